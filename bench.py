@@ -4,13 +4,17 @@ forward + backward + gradient all-reduce + SGD step) on 8-frame, 2-identity, 224
 
     python bench.py --gpus N --steps K --warmup W         (N > 1: launched by torch.distributed.run, one rank per GPU)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0: clips/s and ms_per_step of the K timed steps.  A plain run does nothing else: set-up, W warm-up
+steps, the K timed steps, the line.  --dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+--full adds the measurements that cost steps or runs of their own, with extra objects in the line:
   roofline       the TIME-DOMINANT kernel family of the step (the TimeSformer's weight-gradient GEMMs, fp32 MFMA), timed live
                  with HIP events on the stream it is launched on, over the timed region
   roofline_ff1   the largest single GEMM (FF1 + GEGLU epilogue), same method (round 1's roofline object, kept for continuity)
   roofline_hbm   the dominant HBM-bound kernel family (EfficientNet depthwise data gradient): algorithmic GB/s vs 8 TB/s
+  host_enqueue_ms_per_step (and the exposed all-reduce time per rank): three more steps after the timed region
   phases         event-timed phases of the step + the fraction of the fp32-MFMA peak each network reaches
   forward_only   inference clips/s (eval-mode and train-mode BatchNorm), seeds: ms/step on synthetic seeds 0/1/2 + median
+  fp32_mfma_pipe, attention_modules, last_layer_dead_rows_pruned, deterministic, other_configs (configs 2 and 5)
   cpu_baseline   the CPU oracle (restatement pinned to the reference) timed on this host's cores, rank 0, N == 1 only
 --config 2 | 5 time BASELINE.json's other single-GPU configurations (B=16 1 identity; Xception "XS" B=32 x 16 frames x 3 ids).
 """
@@ -362,6 +366,45 @@ def other_config_leg(config, dev, steps=6, warm=10):
     return out
 
 
+DUMP_SAMPLE = 8192           # elements per tensor written by dump_outputs (every element of a smaller tensor)
+DUMP_LIMIT = 64 << 20        # bytes per dump
+
+
+def dump_outputs(outdir, loss, models, seed=0):
+    """Write what one training step hands its caller to `outdir` as float32 .npy files: `loss.npy`, and for every (prefix, module)
+    of `models` `<prefix>_state.npy` (parameters and BatchNorm running statistics after the optimizer step, state_dict order) and
+    `<prefix>_grad.npy` (parameter gradients, named_parameters order), each the concatenation of its tensors.  A tensor of more than
+    DUMP_SAMPLE elements contributes DUMP_SAMPLE of them, at sorted indices drawn by numpy Philox keyed by (seed, crc32 of its
+    name): the same elements in every run and every build, so two builds can be compared output for output (main seeds the
+    drop-connect draws and starts every step from the seeded weights; the default mode's floating-point atomics leave last-bit
+    differences, MT_DETERMINISTIC=1 none).  Returns {file name: shape written}."""
+    import zlib
+    import numpy as np
+
+    def sample(name, t):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            rng = np.random.Generator(np.random.Philox(key=[int(seed), zlib.crc32(name.encode())]))
+            idx = np.sort(rng.choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        return flat.float()
+
+    arrays = {"loss": loss.detach().reshape(1).float()}
+    for prefix, m in models:
+        arrays[prefix + "_state"] = torch.cat([sample(k, v) for k, v in m.state_dict().items() if v.is_floating_point()])
+        arrays[prefix + "_grad"] = torch.cat([sample(k, p.grad) for k, p in m.named_parameters() if p.grad is not None])
+    total = sum(t.numel() * 4 for t in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT >> 20} MB")
+    os.makedirs(outdir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        written[name] = a.shape
+    return written
+
+
 def free_port():
     import socket
     with socket.socket() as so:
@@ -443,13 +486,18 @@ def main():
     ap.add_argument("--batch-per-gpu", type=int, default=None)
     ap.add_argument("--frames", type=int, default=None)
     ap.add_argument("--ragged", action="store_true", help="config-3 variant with the last slot of each identity padded")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the phase / forward-only / seed legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline probes, host enqueue time, the extra legs and the CPU baseline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, updated state and gradients to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the phase / forward-only / seed / other-config legs")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--force-reducer", action="store_true",
                     help="single-GPU check of the multi-GPU step: 1-rank RCCL group + the overlapped gradient reducer")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     wl = dict(WORKLOADS[a.config])
     if a.batch_per_gpu:
         wl["B"] = a.batch_per_gpu
@@ -469,6 +517,8 @@ def main():
     if a.stub:
         return stub_main(a, rank, world)
     torch.cuda.set_device(local_rank)
+    # the CUDA generator seeds itself from the OS in every process: seeded here, drop-connect draws the same uniforms in every run
+    torch.cuda.manual_seed(rank)
     dev = f"cuda:{local_rank}"
     pinned = pin_launch_thread(local_rank, world)
     if world > 1 or a.force_reducer:
@@ -501,7 +551,14 @@ def main():
                if world > 1 or a.force_reducer else None)
     reducer_path = "none" if reducer is None else "overlapped"
 
+    # every step starts from the seeded weights: repeated SGD steps on one batch are unstable here (the loss climbs from 0.77 to 2.2
+    # in three steps) and multiply the last-bit differences of the floating-point atomics by ~1000 per step, so without the restore
+    # two runs would compute different steps; the restore is one multi-tensor copy (in place: the engines see the version bump)
+    live = [t for m in (ef, tsf) for t in m.state_dict().values() if t.is_floating_point()]
+    seeded = [t.clone() for t in live]
+
     def step(bt=None):
+        torch._foreach_copy_(live, seeded)
         return harness.train_step(ef, tsf, opt, batch if bt is None else bt, reducer)
 
     if reducer is not None:
@@ -517,19 +574,20 @@ def main():
             reducer_path = "flat"
     for _ in range(a.warmup):
         step()
-    # live kernel timing over the timed region, HIP events on the stream each kernel is launched on:
-    #   the TimeSformer's weight-gradient GEMMs (TN, plain operands; side stream) = the time-dominant kernel family of the step,
-    #   FF1 + GEGLU (the largest single GEMM), the EfficientNet depthwise data gradient (the largest HBM-bound family)
-    # (mt_gemm launches: the in-kernel split / fp32 pipe; mt_gemm_planes launches: the plane path -- whichever the engine runs)
-    p_wgrad = {"match": lambda d: d.op == lib.OP_TN and d.prologue == lib.PRO_NONE and d.b_prologue == lib.BPRO_NONE,
-               "match_planes": lambda d: d.op == lib.OP_TN, "events": []}
-    p_ff1 = {"match": lambda d: d.epilogue == lib.EPI_GEGLU, "match_planes": lambda d: d.epilogue == lib.EPI_GEGLU, "events": []}
-    p_dw = {"name": "dwconv_dgrad", "events": []}
-    if reducer is not None and hasattr(reducer, "time_exposed"):
-        reducer.time_exposed = True
-    lib.PROFILE = [p_ff1, p_wgrad, p_dw]
     from mintime_amd import plans
-    plans.PROBE_MASK[0] = (1 << lib.TAG_WGRAD) | (1 << lib.TAG_FF1) | (1 << lib.TAG_DWCONV_DGRAD)
+    if a.full:
+        # live kernel timing over the timed region, HIP events on the stream each kernel is launched on:
+        #   the TimeSformer's weight-gradient GEMMs (TN, plain operands; side stream) = the time-dominant kernel family of the step,
+        #   FF1 + GEGLU (the largest single GEMM), the EfficientNet depthwise data gradient (the largest HBM-bound family)
+        # (mt_gemm launches: the in-kernel split / fp32 pipe; mt_gemm_planes launches: the plane path -- whichever the engine runs)
+        p_wgrad = {"match": lambda d: d.op == lib.OP_TN and d.prologue == lib.PRO_NONE and d.b_prologue == lib.BPRO_NONE,
+                   "match_planes": lambda d: d.op == lib.OP_TN, "events": []}
+        p_ff1 = {"match": lambda d: d.epilogue == lib.EPI_GEGLU, "match_planes": lambda d: d.epilogue == lib.EPI_GEGLU, "events": []}
+        p_dw = {"name": "dwconv_dgrad", "events": []}
+        if reducer is not None and hasattr(reducer, "time_exposed"):
+            reducer.time_exposed = True
+        lib.PROFILE = [p_ff1, p_wgrad, p_dw]
+        plans.PROBE_MASK[0] = (1 << lib.TAG_WGRAD) | (1 << lib.TAG_FF1) | (1 << lib.TAG_DWCONV_DGRAD)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -544,22 +602,27 @@ def main():
     dt = time.perf_counter() - t0
     lib.PROFILE = None
     plans.PROBE_MASK[0] = 0
-    # launch-side cost: wall time the host needs to ENQUEUE one step (~790 launches through ctypes) onto an idle device, i.e. without
-    # back-pressure from a full queue.  The step is device-bound as long as this stays below ms_per_step.
-    t_enq = 0.0
-    for _ in range(3):
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, loss, [("extractor", ef), ("timesformer", tsf)])
+    t_enq = exposed = None
+    if a.full:
+        # launch-side cost: wall time the host needs to ENQUEUE one step (~790 launches through ctypes) onto an idle device, i.e. without
+        # back-pressure from a full queue.  The step is device-bound as long as this stays below ms_per_step.
+        t_enq = 0.0
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step()
+            t_enq += time.perf_counter() - t1
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step()
-        t_enq += time.perf_counter() - t1
-    torch.cuda.synchronize()
-    t_enq /= 3
-    exposed = reducer.exposed_ms() if reducer is not None and hasattr(reducer, "exposed_ms") else None
-    if reducer is not None and hasattr(reducer, "time_exposed"):
-        reducer.time_exposed = False
+        t_enq /= 3
+        exposed = reducer.exposed_ms() if reducer is not None and hasattr(reducer, "exposed_ms") else None
+        if reducer is not None and hasattr(reducer, "time_exposed"):
+            reducer.time_exposed = False
     # per-rank readings (first contact with an 8-GPU node should be diagnostic, not one number): step time, host enqueue time and
-    # the exposed part of the gradient all-reduce of every rank
-    mine = torch.tensor([1e3 * dt / a.steps, 1e3 * t_enq, -1.0 if exposed is None else exposed], device=dev, dtype=torch.float64)
+    # the exposed part of the gradient all-reduce of every rank (the last two with --full)
+    mine = torch.tensor([1e3 * dt / a.steps, -1.0 if t_enq is None else 1e3 * t_enq, -1.0 if exposed is None else exposed],
+                        device=dev, dtype=torch.float64)
     per_rank = [mine]
     if world > 1:
         per_rank = [torch.zeros_like(mine) for _ in range(world)]
@@ -574,9 +637,6 @@ def main():
         clips_s = world * B * a.steps / dt
         flop_step = 3 * wl["flop_fwd"]
         headline = a.config == 3 and B == 32 and frames == 8 and not a.ragged
-        n_w, t_w, f_w = _probe_summary(p_wgrad, lib.TAG_WGRAD)
-        n_f, t_f, f_f = _probe_summary(p_ff1, lib.TAG_FF1)
-        n_d, t_d, b_d = _probe_summary(p_dw, lib.TAG_DWCONV_DGRAD)
         pmc = lambda key: (committed_counters(key) or {}) if headline else {}
         split_on = lib.gemm_split_enabled()
         out = {
@@ -588,52 +648,59 @@ def main():
             "config": {"workload": f"{wl['name']}: {'Xception' if a.config == 5 else 'EfficientNet-B0'} + SizeInvariantTimeSformer(dim 512, "
                                    f"depth 9, heads 8), B={B}/GPU, {frames} frames, {wl['ids']} identit{'y' if wl['ids'] == 1 else 'ies'} "
                                    f"{'(identity-masked' + (', last slot of each identity padded' if a.ragged else '') + ')'}, 224x224 crops, "
-                                   "random-init seeded weights, train-mode BN" + (" + drop-connect 0.2" if a.config != 5 else "")
+                                   "random-init seeded weights (restored before every step), train-mode BN" + (" + drop-connect 0.2" if a.config != 5 else "")
                                    + ", step = fwd + BCE loss + bwd"
                                    + (" + RCCL grad all-reduce" if world > 1 else "") + " + SGD(lr .01, wd 1e-4)",
                        "global_batch": world * B, "frames": frames, "parallelism": f"dp{world}", "reducer_path": reducer_path,
-                       "per_rank": {"ms_per_step": [r[0] for r in per_rank], "host_enqueue_ms_per_step": [r[1] for r in per_rank],
-                                    "allreduce_exposed_ms": [None if r[2] < 0 else r[2] for r in per_rank],
+                       "per_rank": {"ms_per_step": [r[0] for r in per_rank],
+                                    **({"host_enqueue_ms_per_step": [r[1] for r in per_rank],
+                                        "allreduce_exposed_ms": [None if r[2] < 0 else r[2] for r in per_rank]} if a.full else {}),
                                     "launch_thread_cores": pinned},
                        "model_tflops": round(clips_s * flop_step / 1e12, 2),
                        "model_frac_vs_fp32_mfma": round(clips_s * flop_step / (world * PEAK_FP32_MFMA), 4),
                        "matrix_pipe": SPLIT_PIPE + "; convolution GEMMs with operand prologues and K < 512: v_mfma_f32_32x32x2_f32"
                        if split_on else "v_mfma_f32_32x32x2_f32 (MT_GEMM_SPLIT=0)",
                        "loss": round(float(loss.item()), 5),
-                       "host_enqueue_ms_per_step": round(1e3 * t_enq, 3),
+                       **({"host_enqueue_ms_per_step": round(1e3 * t_enq, 3)} if a.full else {}),
                        "launch_plans": {"enabled": plans.ENABLED, **{k: plans.STATS[k] for k in ("recorded", "replayed")},
                                         "calls_per_phase": sorted(pl.ops for np_ in plans.ALL for pl in (np_.fwd, np_.bwd)
                                                                   if pl is not None)}},
-            # the time-dominant kernel family: in-step duration (next to the main stream's data-gradient GEMMs), all launches summed
-            "roofline": {"bound": "mfma", "kernel": WGRAD_KERNEL[split_on],
-                         **mfma_roofline(f_w / t_w if t_w else None, split_on),
-                         "traffic": pmc("tsf_wgrad").get("bytes_per_launch"), "traffic_unit": "bytes/launch (family mean)",
-                         "traffic_source": pmc("tsf_wgrad").get("source"),
-                         # the counter fields of this object and of roofline_ff1 / roofline_hbm are NOT measured in this run: they are read
-                         # from profiles/*_pmc_families.json (hash-tied to csrc/), collected with the weight-gradient stream off
-                         "pmc_mode": "serialised (side stream off), committed file, hash-tied to csrc/" if pmc("tsf_wgrad") else None,
-                         "algorithmic_bytes": pmc("tsf_wgrad").get("algorithmic_bytes_per_launch"),
-                         # matrix-pipe counters of the same family from the hash-tied PMC passes (serialised: side stream off):
-                         # SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs), clock = GRBM_GUI_ACTIVE / 8 / wall
-                         "mfma_busy_frac": pmc("tsf_wgrad").get("mfma_busy_frac"),
-                         "effective_clock_ghz": pmc("tsf_wgrad").get("effective_clock_ghz"),
-                         "mfma_busy_vs_algorithmic": pmc("tsf_wgrad").get("busy_vs_algorithmic"),
-                         "launches_timed": n_w, "launches_per_step": n_w // max(a.steps, 1),
-                         "avg_launch_us": round(t_w / max(n_w, 1) * 1e6, 1), "flops_per_launch": f_w / max(n_w, 1),
-                         "ms_per_step": round(t_w / max(a.steps, 1) * 1e3, 3)},
-            "roofline_ff1": {"bound": "mfma", "kernel": "mt::gemm_" + ("planes" if split_on else "dma")
-                                                        + "_kernel<128x128, NT, EPI_GEGLU> (FF1 512->4096 + GEGLU, M=B*393"
-                                                        + ("; emits h as operand planes)" if split_on else ")"),
-                             **mfma_roofline(f_f / t_f if t_f else None, split_on),
-                             "traffic": pmc("tsf_ff1").get("bytes_per_launch"), "traffic_unit": "bytes/launch",
-                             "algorithmic_bytes": pmc("tsf_ff1").get("algorithmic_bytes_per_launch"),
-                             "mfma_busy_frac": pmc("tsf_ff1").get("mfma_busy_frac"),
-                             "effective_clock_ghz": pmc("tsf_ff1").get("effective_clock_ghz"),
-                             "mfma_busy_vs_algorithmic": pmc("tsf_ff1").get("busy_vs_algorithmic"),
-                             "launches_timed": n_f, "avg_launch_us": round(t_f / max(n_f, 1) * 1e6, 1),
-                             "flops_per_launch": f_f / max(n_f, 1)},
         }
-        if n_d:
+        if a.full:
+            n_w, t_w, f_w = _probe_summary(p_wgrad, lib.TAG_WGRAD)
+            n_f, t_f, f_f = _probe_summary(p_ff1, lib.TAG_FF1)
+            n_d, t_d, b_d = _probe_summary(p_dw, lib.TAG_DWCONV_DGRAD)
+            out.update({
+                # the time-dominant kernel family: in-step duration (next to the main stream's data-gradient GEMMs), all launches summed
+                "roofline": {"bound": "mfma", "kernel": WGRAD_KERNEL[split_on],
+                             **mfma_roofline(f_w / t_w if t_w else None, split_on),
+                             "traffic": pmc("tsf_wgrad").get("bytes_per_launch"), "traffic_unit": "bytes/launch (family mean)",
+                             "traffic_source": pmc("tsf_wgrad").get("source"),
+                             # the counter fields of this object and of roofline_ff1 / roofline_hbm are NOT measured in this run: they are read
+                             # from profiles/*_pmc_families.json (hash-tied to csrc/), collected with the weight-gradient stream off
+                             "pmc_mode": "serialised (side stream off), committed file, hash-tied to csrc/" if pmc("tsf_wgrad") else None,
+                             "algorithmic_bytes": pmc("tsf_wgrad").get("algorithmic_bytes_per_launch"),
+                             # matrix-pipe counters of the same family from the hash-tied PMC passes (serialised: side stream off):
+                             # SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs), clock = GRBM_GUI_ACTIVE / 8 / wall
+                             "mfma_busy_frac": pmc("tsf_wgrad").get("mfma_busy_frac"),
+                             "effective_clock_ghz": pmc("tsf_wgrad").get("effective_clock_ghz"),
+                             "mfma_busy_vs_algorithmic": pmc("tsf_wgrad").get("busy_vs_algorithmic"),
+                             "launches_timed": n_w, "launches_per_step": n_w // max(a.steps, 1),
+                             "avg_launch_us": round(t_w / max(n_w, 1) * 1e6, 1), "flops_per_launch": f_w / max(n_w, 1),
+                             "ms_per_step": round(t_w / max(a.steps, 1) * 1e3, 3)},
+                "roofline_ff1": {"bound": "mfma", "kernel": "mt::gemm_" + ("planes" if split_on else "dma")
+                                                            + "_kernel<128x128, NT, EPI_GEGLU> (FF1 512->4096 + GEGLU, M=B*393"
+                                                            + ("; emits h as operand planes)" if split_on else ")"),
+                                 **mfma_roofline(f_f / t_f if t_f else None, split_on),
+                                 "traffic": pmc("tsf_ff1").get("bytes_per_launch"), "traffic_unit": "bytes/launch",
+                                 "algorithmic_bytes": pmc("tsf_ff1").get("algorithmic_bytes_per_launch"),
+                                 "mfma_busy_frac": pmc("tsf_ff1").get("mfma_busy_frac"),
+                                 "effective_clock_ghz": pmc("tsf_ff1").get("effective_clock_ghz"),
+                                 "mfma_busy_vs_algorithmic": pmc("tsf_ff1").get("busy_vs_algorithmic"),
+                                 "launches_timed": n_f, "avg_launch_us": round(t_f / max(n_f, 1) * 1e6, 1),
+                                 "flops_per_launch": f_f / max(n_f, 1)},
+            })
+        if a.full and n_d:
             out["roofline_hbm"] = {"bound": "hbm", "kernel": "EfficientNet depthwise-conv data gradient (dwconv_dgrad_tiled_kernel, 16 "
                                                              "launches/step, main stream, next to the side stream's weight gradients)",
                                    "achieved": round(b_d / t_d / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
@@ -641,7 +708,7 @@ def main():
                                    "traffic": pmc("ef_dwconv_dgrad").get("bytes_per_step"), "traffic_unit": "bytes/step (16 launches)",
                                    "algorithmic_bytes": round(b_d / max(a.steps, 1)), "launches_timed": n_d,
                                    "ms_per_step": round(t_d / max(a.steps, 1) * 1e3, 3)}
-        if world == 1 and not a.no_extras:
+        if a.full and world == 1 and not a.no_extras:
             ph = phases_leg(ef, tsf, opt, batch)
             tsf_flop = 3 * B * (wl["flop_fwd"] - (2 * 3076278016 if a.config != 5 else 2 * 72813297152))
             ef_flop = 3 * wl["flop_fwd"] * B - tsf_flop
@@ -728,9 +795,9 @@ def main():
                     out["deterministic"] = {"error": f"{type(e).__name__}: {e}"}
                 finally:
                     lib.set_deterministic(False)
-        if world == 1 and not a.no_extras and headline:
+        if a.full and world == 1 and not a.no_extras and headline:
             out["other_configs"] = {"config2": other_config_leg(2, dev), "config5": other_config_leg(5, dev)}
-        if world == 1 and not a.no_cpu_baseline and a.config != 5:
+        if a.full and world == 1 and not a.no_cpu_baseline and a.config != 5:
             out["cpu_baseline"] = cpu_baseline_subprocess(frames)
     line = json.dumps(out) if rank == 0 else None
     if world > 1 or a.force_reducer:

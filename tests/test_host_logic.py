@@ -601,6 +601,33 @@ def test_bench_drops_pmc_counters_measured_on_other_sources(tmp_path, monkeypatc
     assert bench.mfma_roofline(100e12, False)["peak"] == 157.3
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample_of_state_and_gradients(tmp_path):
+    """`bench.py --dump-outputs DIR` after the timed steps: the loss, the floating state tensors and the parameter gradients as float32
+    .npy files; a tensor larger than DUMP_SAMPLE contributes the same sorted, seeded sample of its elements in every run."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(300, 100), torch.nn.BatchNorm1d(100))
+    m(torch.randn(4, 300)).square().sum().backward()
+    loss = torch.tensor(0.25)
+    w1 = bench.dump_outputs(str(tmp_path / "a"), loss, [("net", m)])
+    w2 = bench.dump_outputs(str(tmp_path / "b"), loss, [("net", m)])
+    n = bench.DUMP_SAMPLE                                                    # the 30000-element weight is sampled, the rest whole
+    assert w1 == w2 == {"loss": (1,), "net_state": (n + 100 + 4 * 100,), "net_grad": (n + 100 + 2 * 100,)}
+    for name in w1:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [0.25]
+    state, grad = np.load(tmp_path / "a" / "net_state.npy"), np.load(tmp_path / "a" / "net_grad.npy")
+    assert np.isin(state[:n], m[0].weight.detach().reshape(-1).numpy()).all()     # a sample of the tensor's own values
+    assert np.isin(grad[:n], m[0].weight.grad.reshape(-1).numpy()).all()
+    assert np.array_equal(state[-100:], m[1].running_var.numpy())
+    assert np.array_equal(grad[-100:], m[1].bias.grad.numpy())
+
+
 def test_plane_tensor_layout_spec():
     """The operand format of mt_gemm_planes, restated with plain torch on the CPU: planes[3][Rp/32][Cp/16][32][16] bf16 holding the
     exact three-piece split x = p0 + p1 + p2 (round-to-nearest bf16 at each level) with zero padding -- what every producer kernel

@@ -8,9 +8,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("csv")
 ap.add_argument("--start", default="stem_mfma_kernel", help="substring of the kernel that starts a step (the stem kernel)")
 ap.add_argument("--steps-from-end", type=int, default=0,
-                help="which step of the trace: bench.py ends with three enqueue-timing steps that follow a synchronize (the host is not "
+                help="which step of the trace: bench.py --full ends with three enqueue-timing steps that follow a synchronize (the host is not "
                      "ahead there and its launch latency shows as device idle); 4-9 from the end lie inside the timed region of "
-                     "`bench.py --steps 8`.  0 (default): the one of those six with the median span (a single step can catch a host "
+                     "`bench.py --full --steps 8`.  0 (default): the one of those six with the median span (a single step can catch a host "
                      "hiccup of the profiler: one evidence run showed a 2.9 ms gap in step 6 and none in its neighbours)")
 ap.add_argument("--top", type=int, default=40, help="symbols listed per queue")
 a = ap.parse_args()
