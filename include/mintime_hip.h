@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MT_VERSION 119
+#define MT_VERSION 120
 
 int mt_version(void);
 const char* mt_last_error(void);
@@ -527,6 +527,26 @@ int mt_bn_act_fwd_planes(const float* z, const float* scale, const float* shift,
                          const float* rowscale, int rows_per_group, void* y_planes, void* stream);
 int mt_bn_swish_gate_planes(const float* z, const float* scale, const float* shift, const float* gate, int hw, void* planes, int rows,
                             int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Baseline head (reference models/baseline.py:15-37, `--model 0`): AdaptiveAvgPool2d(1) -> Linear(dim, mlp) -> Linear(mlp, 1) over
+ * per-crop features, for num-classes 1 only (csrc/baseline.hip).  With one class and no nonlinearity between the Linears the head is
+ * the vector v = W1^T w2 and the scalar c0 = w2 . b1 + b2:  logit_i = mean_p(x_i[p, :]) . v + c0.  No GEMM runs and no atomic is
+ * issued: every sum is in a fixed order, so the results are the same bits run after run (deterministic mode or not).
+ * Shapes: x holds n crops of C channels and hw pixels, layout 0 = NHWC (x[i][p][c], the extractors' own output) or 1 = NCHW
+ * (x[i][c][p]); W1 [m][C], b1 [m], w2 [m] (the single row of the second Linear's weight), b2 [1].  C % 4 == 0, n <= 65535,
+ * C * hw < 2^31; offsets past one crop are 64-bit.  x, dx, vc, work, W1 and dW1 are 16-byte aligned.
+ * mt_baseline_head_fwd: vc [C + 1] = (v, c0) (kept for the backward); pooled [n][C] = the mean features (NULL: not written -- an
+ *   inference forward); part = scratch of n * ceil(C / 256) floats; logits [n].
+ * mt_baseline_head_bwd: from dlogits [n] = dL/dlogit, the gradients whose pointer is not NULL: dW1 [m][C], db1 [m], dW2 [m], db2 [1]
+ *   (these need pooled, W1, b1, w2 and work = scratch of (ceil(n / 32) + 1) * (C + 4) floats) and dx = dlogit_i v / hw broadcast over
+ *   the crop's pixels, written in `layout` (the input's).  Nothing is launched for a NULL output.
+ * ------------------------------------------------------------------------------------------------ */
+int mt_baseline_head_fwd(const float* x, int layout, int n, int hw, int C, int m, const float* w1, const float* b1, const float* w2,
+                         const float* b2, float* vc, float* pooled, float* part, float* logits, void* stream);
+int mt_baseline_head_bwd(const float* dlogits, const float* pooled, const float* vc, int n, int hw, int C, int m, const float* w1,
+                         const float* b1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, float* dx, int layout,
+                         float* work, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Launch plans (the caller side of the step: reference train.py:332-378, the Python loop that issues every op).

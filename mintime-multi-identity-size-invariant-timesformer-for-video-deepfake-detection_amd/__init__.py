@@ -18,5 +18,8 @@ from .timesformer import SizeInvariantTimeSformer  # noqa: F401
 from .efficientnet import EfficientNet  # noqa: F401
 from . import xception as xception_module, xception_engine  # noqa: F401
 from .xception import xception, Xception  # noqa: F401
+from . import baseline  # noqa: F401,E402
+from .baseline import Baseline  # noqa: F401,E402
 
-__all__ = ["arch", "synth", "lib", "timesformer", "tsf_engine", "SizeInvariantTimeSformer", "efficientnet", "effnet_engine", "EfficientNet"]
+__all__ = ["arch", "synth", "lib", "timesformer", "tsf_engine", "SizeInvariantTimeSformer", "efficientnet", "effnet_engine", "EfficientNet",
+           "baseline", "Baseline"]

@@ -137,6 +137,24 @@ def default_tsf_config(channels: int = 1280, num_frames: int = 8):
     }
 
 
+def default_baseline_config(dim: int = 1280, num_frames: int = 16):
+    """The shipped config/baseline.yaml (`--model 0`): dim 1280 for EfficientNet-B0 features, 2048 for Xception's."""
+    return {
+        "model": {"image-size": 224, "num-classes": 1, "dim": dim, "mlp-dim": 512, "num-frames": num_frames, "max-identities": 2},
+        "training": {"lr": 0.01, "weight-decay": 0.0001, "bs": 8, "val_bs": 8, "optimizer": "SGD",
+                     "scheduler": "cosinelr", "gamma": 0.1, "step-size": 5, "augmentation": "max"},
+        "test": {"bs": 1},
+    }
+
+
+def baseline_state_spec(cfg):
+    """Ordered (key, shape, kind) for Baseline (reference models/baseline.py:24-27); kind in {lin_w, lin_b}."""
+    m = cfg["model"]
+    dim, mlp, k = m["dim"], m["mlp-dim"], m["num-classes"]
+    return [("mlp_head.0.weight", (mlp, dim), "lin_w"), ("mlp_head.0.bias", (mlp,), "lin_b"),
+            ("mlp_head.1.weight", (k, mlp), "lin_w"), ("mlp_head.1.bias", (k,), "lin_b")]
+
+
 def tsf_state_spec(cfg):
     """Ordered (key, shape, kind) for SizeInvariantTimeSformer (size_invariant_timesformer.py:172-198).
 

@@ -7,6 +7,7 @@ import torch.nn.functional as F
 from . import arch, optim, synth
 from .efficientnet import EfficientNet
 from .timesformer import SizeInvariantTimeSformer
+from .baseline import Baseline
 
 
 def build_models(num_frames=8, seed=0, device="cuda", require_attention=False, drop_connect_rate=arch.DROP_CONNECT_RATE,
@@ -45,6 +46,26 @@ def make_optimizer(cfg, ef, tsf):
         raise ValueError("Error: Invalid optimizer specified in the config file.")      # train.py:191-193
     # one multi-tensor launch per step instead of torch's foreach kernels (same update rule)
     return (fused if params[0].is_cuda else plain)[kind](params, lr=t["lr"], weight_decay=t["weight-decay"])
+
+
+def build_baseline(num_frames=16, seed=0, device="cuda", extractor=0, drop_connect_rate=arch.DROP_CONNECT_RATE, train_extractor=True):
+    """`--model 0` (train.py:120-138, config/baseline.yaml): extractor 0 = EfficientNet-B0 (dim 1280), 1 = Xception (dim 2048), then
+    the Baseline head.  Returns (config, extractor, model)."""
+    if extractor == 0:
+        ex = EfficientNet.from_name("efficientnet-b0", drop_connect_rate=drop_connect_rate)
+        ex.load_state_dict(synth.effnet_b0_state(seed))
+        dim = 1280
+    else:
+        from .xception import xception
+        ex = xception(num_classes=1, pretrain_path=None)
+        ex.load_state_dict(synth.xception_state(seed))
+        dim = 2048
+    cfg = arch.default_baseline_config(dim, num_frames)
+    model = Baseline(config=cfg)
+    model.load_state_dict(synth.baseline_state(cfg, seed))
+    ex.to(device).train(train_extractor)
+    model.to(device).train()
+    return cfg, ex, model
 
 
 def device_batch(batch, num_frames=8, num_identities=2, seed=0, device="cuda", ragged=False, as_uint8=False):
@@ -91,6 +112,36 @@ def train_step(ef, tsf, optimizer, batch, reducer=None, pos_weight=None):
 def eval_step(ef, tsf, batch):
     """test.py:235-247 / predict.py:401-406: eval forward; returns logits (and attentions if the model was built with them)."""
     return forward(ef, tsf, batch)
+
+
+def baseline_forward(ex, model, batch, freeze_backbone=False):
+    """train.py:341-352 with `--model 0`: per-crop logits of the Baseline head, averaged over the clip's frames."""
+    videos = batch["videos"]
+    b, f, h, w, c = videos.shape
+    x = videos.reshape(b * f, h, w, c).permute(0, 3, 1, 2)                    # train.py:341 (a view)
+    if freeze_backbone:                                                        # train.py:344-346
+        with torch.no_grad():
+            features = ex(x)
+    else:
+        features = ex(x)                                                       # train.py:348
+    y_pred = model(features)                                                   # train.py:351
+    return torch.mean(y_pred.reshape(-1, f), 1).unsqueeze(1)                   # train.py:352 (num-frames = f)
+
+
+def baseline_train_step(ex, model, optimizer, batch, pos_weight=None, freeze_backbone=False):
+    """One `--model 0` optimisation step (train.py:341-378); the optimizer comes from make_optimizer(cfg, ex, model)."""
+    y_pred = baseline_forward(ex, model, batch, freeze_backbone)
+    loss = optim.bce_with_logits(y_pred, batch["labels"], pos_weight)
+    optimizer.zero_grad(set_to_none=True)
+    loss.backward()
+    optimizer.step()
+    return loss
+
+
+@torch.no_grad()
+def baseline_eval_step(ex, model, batch):
+    """test.py:235-244 with `--model 0`: eval forward, frame-averaged logits [B, 1]."""
+    return baseline_forward(ex, model, batch)
 
 
 def aggregate_attentions(attentions, heads, num_frames, frames_per_identity, scale_factor=50000):

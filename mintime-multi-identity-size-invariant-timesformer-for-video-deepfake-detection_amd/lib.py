@@ -149,6 +149,8 @@ PROTOTYPES = {
     "mt_stem_conv_wgrad_valid": [f32p] * 4 + [C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "mt_bn_act_fwd_planes": [f32p, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_void_p, C.c_void_p],
     "mt_bn_swish_gate_planes": [f32p, f32p, f32p, f32p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "mt_baseline_head_fwd": [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [f32p] * 8 + [C.c_void_p],
+    "mt_baseline_head_bwd": [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int] + [f32p] * 8 + [C.c_int, f32p, C.c_void_p],
     "mt_plan_create": [C.POINTER(C.c_void_p)],
     "mt_plan_destroy": [C.c_void_p],
     "mt_plan_record_begin": [C.c_void_p],
@@ -183,7 +185,7 @@ def build(verbose: bool = False):
 
 # MT_VERSION of include/mintime_hip.h this binding was written against (tests/test_host_logic.py keeps the two equal; the package
 # itself does not need the header at run time -- it may be copied or installed without the repository's include/ directory)
-ABI_VERSION = 119
+ABI_VERSION = 120
 
 
 def header_version() -> int:

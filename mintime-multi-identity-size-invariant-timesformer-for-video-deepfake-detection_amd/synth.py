@@ -145,6 +145,22 @@ def tsf_state(cfg, seed: int = 0):
     return sd
 
 
+def baseline_state(cfg, seed: int = 0):
+    """Seeded state-dict with the reference Baseline keys/shapes: weights scaled by 1/sqrt(fan-in), so the hidden units and the
+    logits stay O(1) on O(1) pooled features."""
+    sd = {}
+    for i, (key, shape, kind) in enumerate(arch.baseline_state_spec(cfg)):
+        g = _rng(seed, 30000 + i)
+        if kind == "lin_w":
+            w = g.standard_normal(shape) / np.sqrt(shape[1])
+        elif kind == "lin_b":
+            w = g.standard_normal(shape) * 0.1
+        else:
+            raise KeyError(kind)
+        sd[key] = _t(w)
+    return sd
+
+
 def identity_split(num_frames: int, num_identities: int):
     """Slots per identity with ample faces (deepfakes_dataset.py:50-53,153-186):
     8/1 -> [8]; 8/2 -> [4,4]; 16/3 -> [7,5,4] ..."""

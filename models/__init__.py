@@ -2,4 +2,6 @@
 
     from models.efficientnet.efficientnet_pytorch import EfficientNet      (reference train.py:27)
     from models.size_invariant_timesformer import SizeInvariantTimeSformer (reference train.py:28)
+    from models.baseline import Baseline                                   (reference train.py:32)
+    from models.xception import xception                                   (reference train.py:33)
 """

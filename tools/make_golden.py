@@ -6,6 +6,7 @@ Runs only in the build container (the reference does not exist on the GPU box). 
 reference's source enters the repo: the fixtures are inputs' checksums and output tensors.
 
     python tools/make_golden.py            # writes every fixture
+    GOLDEN_ONLY=baseline python tools/make_golden.py   # only baseline_head.npz and baseline_e2e_train.npz (`--model 0`)
 """
 import json
 import os
@@ -483,6 +484,106 @@ def xc_case(name, n_img, training, seed):
          n_img=n_img, training=int(training), seed=seed, **extra, **grads)
 
 
+def import_reference_baseline():
+    """The reference's models/baseline.py: it imports cv2, timm, torchsummary and efficientnet_pytorch at file scope and uses none."""
+    placeholder_modules("cv2", "timm", "torchsummary", "efficientnet_pytorch")
+    return import_reference_file("_ref_baseline", os.path.join("models", "baseline.py"))
+
+
+def _dense_grad_record(out, tag, key, g, seed):
+    """Norm, max |g|, 256-element strided sample and the whole-tensor checksum pair (sum g, sum g*r; tests/util.probe_vector)."""
+    from tests.util import probe_vector
+    g = g.reshape(-1)
+    step = max(1, g.numel() // 256)
+    out["gnorm64." + tag + key] = g.norm()
+    out["gabsmax64." + tag + key] = g.abs().max()
+    out["gsample64." + tag + key] = g[::step][:256].clone()
+    out["gsum64." + tag + key] = g.sum()
+    out["gdot64." + tag + key] = (g * torch.from_numpy(probe_vector(tag + key, g.numel(), seed))).sum()
+
+
+def _head_grads(out, head, x, suffix, seed):
+    """Every head gradient of one reference run: the small ones whole, mlp_head.0.weight [512, C] as every 16th row plus the norm and
+    checksum pair, the input gradient as its value at pixel (0, 0) -- AdaptiveAvgPool2d(1)'s backward spreads dL/dpooled / hw over the
+    pixels, so every pixel holds the same value (checked here)."""
+    from tests.util import probe_vector
+    named = dict(head.named_parameters())
+    for key in ("mlp_head.0.bias", "mlp_head.1.weight", "mlp_head.1.bias"):
+        out[f"g{suffix}.{key}"] = named[key].grad.clone()
+    gw = named["mlp_head.0.weight"].grad
+    out[f"grows{suffix}.mlp_head.0.weight"] = gw[::16].clone()
+    out[f"gnorm{suffix}.mlp_head.0.weight"] = gw.norm()
+    out[f"gsum{suffix}.mlp_head.0.weight"] = gw.sum()
+    out[f"gdot{suffix}.mlp_head.0.weight"] = (gw.reshape(-1) * torch.from_numpy(probe_vector("mlp_head.0.weight", gw.numel(), seed))).sum()
+    if x is not None:
+        gx = x.grad
+        assert bool((gx == gx[:, :, :1, :1]).all()), "input gradient not constant over the pixels"
+        out[f"gx{suffix}"] = gx[:, :, 0, 0].clone()
+
+
+def baseline_head_case(ref, name, clips=3, frames=16, channels=1280, seed=11):
+    """The Baseline head alone (reference models/baseline.py) on seeded features (synth.features: NHWC storage seen as NCHW, like the
+    extractors' output), then the callers' frame mean and BCE (train.py:350-352, 414-419); fp32 and fp64 runs of the reference."""
+    cfg = arch.default_baseline_config(channels, frames)
+    sd = synth.baseline_state(cfg, seed)
+    feats = synth.features(clips, frames, channels, seed)
+    feats = feats.reshape(clips * frames, *feats.shape[2:])
+    labels = torch.from_numpy(np.random.Generator(np.random.Philox(key=[seed, 777])).integers(0, 2, clips).astype(np.float32))
+    out = {}
+    for suffix, dtype in (("", torch.float32), ("64", torch.float64)):
+        head = ref.Baseline(config=cfg)
+        head.load_state_dict(sd, strict=True)
+        head.to(dtype).train()
+        x = feats.to(dtype).detach().requires_grad_(True)
+        y = head(x)
+        yc = torch.mean(y.reshape(-1, frames), axis=1).unsqueeze(1)
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(yc, labels.unsqueeze(1).to(dtype))
+        loss.backward()
+        out.update({"logits" + suffix: y.detach(), "clip_logits" + suffix: yc.detach(), "loss" + suffix: loss.detach()})
+        _head_grads(out, head, x, suffix, seed)
+    keys = ref.Baseline(config=cfg).state_dict()
+    save(name, state_keys=np.asarray(list(keys)), state_shapes=np.asarray(json.dumps([list(v.shape) for v in keys.values()])),
+         input_sum=checksum(feats), labels=labels, w1_sum=checksum(sd["mlp_head.0.weight"]), **{"w." + k: v for k, v in sd.items()
+                                                                                              if k != "mlp_head.0.weight"},
+         clips=clips, frames=frames, channels=channels, seed=seed, **out)
+
+
+def baseline_e2e_case(EF, ref, name, batch=2, frames=16, seed=12):
+    """`--model 0` training step of the reference (train.py:341-368): EfficientNet-B0 in train mode (drop-connect 0) -> Baseline -> frame
+    mean -> BCE, in fp64 (the exact arithmetic) and fp32 (whose distance from fp64 is the floor each extractor gradient is gated by)."""
+    cfg = arch.default_baseline_config(1280, frames)
+    inp = synth.clip_inputs(batch, frames, 1, seed)
+    out, g32 = {}, {}
+    for suffix, dtype in (("32", torch.float32), ("64", torch.float64)):
+        ef, _ = build_ef(EF, seed, True, dtype)
+        head = ref.Baseline(config=cfg)
+        head.load_state_dict(synth.baseline_state(cfg, seed), strict=True)
+        head.to(dtype).train()
+        v = inp["videos"].to(dtype)
+        b, f, h, w, c = v.shape
+        feats = ef(v.reshape(b * f, h, w, c).permute(0, 3, 1, 2))
+        y = head(feats)
+        yc = torch.mean(y.reshape(-1, frames), axis=1).unsqueeze(1)
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(yc, inp["labels"].unsqueeze(1).to(dtype))
+        loss.backward()
+        if suffix == "32":
+            g32 = {k: p.grad.double().clone() for k, p in ef.named_parameters() if p.grad is not None}
+            out["loss32"] = loss.detach()
+            continue
+        out.update({"logits64": y.detach(), "clip_logits64": yc.detach(), "loss64": loss.detach()})
+        _head_grads(out, head, None, "64", seed)
+        for key, prm in ef.named_parameters():
+            if prm.grad is None:
+                continue
+            _dense_grad_record(out, "ef.", key, prm.grad, seed)
+            out["gfloor." + key] = (g32[key] - prm.grad).norm() / prm.grad.norm().clamp_min(1e-300)
+        msd = ef.state_dict()
+        for key in ("_bn0.running_mean", "_bn0.running_var", "_blocks.3._bn1.running_var", "_blocks.10._bn2.running_mean",
+                    "_bn1.running_mean", "_bn1.running_var"):
+            out["stat64." + key] = msd[key].clone()
+    save(name, input_sum=checksum(inp["videos"]), batch=batch, frames=frames, seed=seed, **out)
+
+
 GRAD_KEYS_XC = ["conv1.weight", "bn1.weight", "conv2.weight", "bn2.bias", "block1.skip.weight", "block1.skipbn.weight",
                 "block1.rep.0.conv1.weight", "block1.rep.0.pointwise.weight", "block1.rep.4.weight", "block3.rep.4.conv1.weight",
                 "block6.rep.4.pointwise.weight", "block6.rep.8.bias", "block12.rep.4.pointwise.weight", "block12.skip.weight",
@@ -501,6 +602,11 @@ def main():
         man[f"tsf_c{c}_f{fr}"] = [[k, list(v.shape), str(v.dtype)] for k, v in t.state_dict().items()]
         man[f"tsf_c{c}_f{fr}_no_weight_decay"] = sorted(t.no_weight_decay())
     only = os.environ.get("GOLDEN_ONLY", "")
+    if only == "baseline":           # the two `--model 0` fixtures alone: nothing else (manifest included) is rewritten
+        ref = import_reference_baseline()
+        baseline_head_case(ref, "baseline_head")
+        baseline_e2e_case(EF, ref, "baseline_e2e_train")
+        return
     if only in ("full2", "full3", "full2ck"):       # full-size steps: minutes of float64 on the host, tens of GB of autograd state -- on request
         if only == "full2":
             e2e_full_case(EF, TSF, "e2e_full_config2", batch=16, frames=8, identities=1, seed=4)
