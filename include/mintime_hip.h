@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MT_VERSION 120
+#define MT_VERSION 121
 
 int mt_version(void);
 const char* mt_last_error(void);
@@ -547,6 +547,71 @@ int mt_baseline_head_fwd(const float* x, int layout, int n, int hw, int C, int m
 int mt_baseline_head_bwd(const float* dlogits, const float* pooled, const float* vc, int n, int hw, int C, int m, const float* w1,
                          const float* b1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, float* dx, int layout,
                          float* work, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * SlowFast R50 (pytorchvideo slowfast_r50, reference train.py:143-147 / test.py:121-125, `--model 2`; csrc/conv3d.hip, slowfast.hip).
+ * Activations are channels-last rows: [N][T][H][W] rows of C floats with a row pitch (ld*, in floats), so a pathway's channel slice of
+ * a concatenated tensor is addressed in place.  No entry point issues an atomic and every sum runs in a fixed order: the results are
+ * the same bits run after run, deterministic mode or not.  Offsets are 64-bit (no 4 GB operand limit).
+ *
+ * mt_conv3d_*: Conv3d as an implicit GEMM on v_mfma_f32_32x32x2_f32, any (kt, kh, kw) kernel, per-axis stride and padding;
+ *   C % 4 == 0, K % 4 == 0, pitches % 4 == 0 (the 3-channel stems take a 4th, zero, channel: mt_sf_ingest writes it).
+ *   fwd:   y[m][co] (+)= sum pro(x)[in(m, tap)][ci] * w[co][tap][ci]  (w = torch weight permuted to [K][kt][kh][kw][C]);
+ *          pro(v) = relu(v * scale[ci] + shift[ci]) when scale is given (BatchNorm + ReLU of the producer; padding stays zero);
+ *          part != NULL: BatchNorm sums of y, stats [2][K] fp64 (sum, sum of squares; written, slot count 1 for mt_bn_finalize);
+ *          part holds mt_conv3d_part_floats(d) floats.
+ *   dgrad: dx[r][ci] (+)= sum dy[out(r, tap)][co] * wt[tap][co][ci]  (wt = weight permuted to [kt][kh][kw][K][C]); a gather, so
+ *          every stride works without atomics.  dx is the gradient of pro(x) (the caller applies the BatchNorm-ReLU adjoint).
+ *   wgrad: dw[co][tap][ci] = sum_m dy[m][co] * pro(x)[in(m, tap)][ci]  (written); split over rows into ws (splits * K * taps * C
+ *          floats; splits = mt_conv3d_wgrad_splits(d)) and added in split order.
+ * mt_sf_bn_relu_fwd: y = relu(z * scale + shift + r), r = res * rscale + rshift (rscale given), res, or 0 (res NULL).
+ * mt_sf_bn_relu_bwd_stats / _apply: the BatchNorm(+ReLU) adjoint.  du = g * mask with mask = (z * scale + shift > 0) when scale is
+ *   given, (m > 0) when m is given, else 1.  stats [2][C] (fp64, written) = (sum du, sum du * (z - mean) * invstd) for
+ *   mt_bn_bwd_finalize (slots 1, count = rows); part holds mt_sf_bn_bwd_part_floats(rows, C) floats.  apply: out (+)= ka du + kb z + kc
+ *   (kabc given) or du.
+ * mt_sf_maxpool_fwd / _bwd: MaxPool3d((1,3,3), (1,2,2), (0,1,1)) over relu(z * scale + shift) (z [NT][H][W][C]), first maximum in
+ *   window order, arg = h * W + w (int32 [rows out][C]); out has pitch ldo.  bwd: din [NT][H][W][C] (written) as a gather.
+ * mt_sf_head_*: ResNetBasicHead of both pathways.  pool: d[b][p][coff + c] = mult * mean of feat over window p (AvgPool3d stride 1,
+ *   p row-major over the (T-kt+1, H-kh+1, W-kw+1) grid; mult = dropout keep / (1 - p) multipliers, NULL = none).  proj: logits[b][j] =
+ *   bias[j] + mean_p W[j] . d[b][p] (Linear at every window, AdaptiveAvgPool3d(1)).  bwd: dW (+=), db (+=), dpool = mult * dd.
+ *   dfeat: the window pooling's adjoint (written, pitch ldf).
+ * mt_sf_ingest: frame j of fidx (int32 [Tout]) -> (v(src[b][fidx[j]][h][w][c]), c < 3; 0) as 4 floats, into out [B][Tsplit][H][W][4]
+ *   for j < Tsplit, else out2 [B][Tout - Tsplit][H][W][4]; v = (u / 255 - 0.45) / 0.225 (normalize) or u; src uint8 (is_u8) or fp32
+ *   with element strides (b, f, h, w, c).  Both pathways in one launch: reference utils.py:166-186 (UniformTemporalSubsample, /255,
+ *   Normalize, PackPathway).
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+  int N, T, H, W, C;                      /* input grid and channels */
+  int To, Ho, Wo, K;                      /* output grid and channels */
+  int kt, kh, kw, st, sh, sw, pt, ph, pw; /* kernel, stride, padding per axis */
+  int64_t ldx, ldy;                       /* row pitches (floats) of the input and output rows */
+} mt_conv3d_desc;
+int64_t mt_conv3d_part_floats(const mt_conv3d_desc* d);
+int mt_conv3d_wgrad_splits(const mt_conv3d_desc* d);
+int mt_conv3d_fwd(const mt_conv3d_desc* d, const float* x, const float* scale, const float* shift, const float* w, float* y, int accumulate,
+                  float* part, double* stats, void* stream);
+int mt_conv3d_dgrad(const mt_conv3d_desc* d, const float* dy, const float* wt, float* dx, int accumulate, void* stream);
+int mt_conv3d_wgrad(const mt_conv3d_desc* d, const float* x, const float* scale, const float* shift, const float* dy, float* dw, float* ws,
+                    int splits, void* stream);
+int mt_sf_bn_relu_fwd(const float* z, int64_t ldz, const float* scale, const float* shift, const float* res, int64_t ldr,
+                      const float* rscale, const float* rshift, float* y, int64_t ldy, int64_t rows, int C, void* stream);
+int64_t mt_sf_bn_bwd_part_floats(int64_t rows, int C);
+int mt_sf_bn_relu_bwd_stats(const float* g, int64_t ldg, const float* z, int64_t ldz, const float* scale, const float* shift, const float* m,
+                            int64_t ldm, const float* mean_invstd, float* part, double* stats, int64_t rows, int C, void* stream);
+int mt_sf_bn_relu_bwd_apply(const float* g, int64_t ldg, const float* z, int64_t ldz, const float* scale, const float* shift, const float* m,
+                            int64_t ldm, const float* kabc, float* out, int64_t ldo, int accumulate, int64_t rows, int C, void* stream);
+int mt_sf_maxpool_fwd(const float* z, const float* scale, const float* shift, float* out, int64_t ldo, int* arg, int64_t NT, int H, int W,
+                      int C, void* stream);
+int mt_sf_maxpool_bwd(const float* dout, int64_t ldd, const int* arg, float* din, int64_t NT, int H, int W, int C, void* stream);
+int mt_sf_head_pool(const float* feat, int64_t ldf, const float* mult, float* d, int B, int T, int H, int W, int C, int kt, int kh, int kw,
+                    int coff, int CT, void* stream);
+int mt_sf_head_proj(const float* d, const float* w, const float* bias, float* logits, int B, int P, int CT, int J, void* stream);
+int mt_sf_head_bwd(const float* g, const float* d, const float* w, const float* mult, float* dw, float* db, float* dpool, int B, int P, int CT,
+                   int J, void* stream);
+int mt_sf_head_dfeat(const float* dpool, float* dfeat, int64_t ldf, int B, int T, int H, int W, int C, int kt, int kh, int kw, int coff,
+                     int CT, void* stream);
+int mt_sf_ingest(const void* src, int is_u8, int64_t sb, int64_t sf, int64_t sh, int64_t sw, int64_t sc, const int* fidx, int Tout,
+                 int Tsplit, int B, int H, int W, int normalize, float* out, float* out2, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Launch plans (the caller side of the step: reference train.py:332-378, the Python loop that issues every op).

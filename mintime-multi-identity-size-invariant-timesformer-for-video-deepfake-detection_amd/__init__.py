@@ -20,6 +20,8 @@ from . import xception as xception_module, xception_engine  # noqa: F401
 from .xception import xception, Xception  # noqa: F401
 from . import baseline  # noqa: F401,E402
 from .baseline import Baseline  # noqa: F401,E402
+from . import slowfast, slowfast_engine  # noqa: F401,E402
+from .slowfast import SlowFast, slowfast_r50, slowfast_input_transform  # noqa: F401,E402
 
 __all__ = ["arch", "synth", "lib", "timesformer", "tsf_engine", "SizeInvariantTimeSformer", "efficientnet", "effnet_engine", "EfficientNet",
-           "baseline", "Baseline"]
+           "baseline", "Baseline", "slowfast", "SlowFast", "slowfast_r50", "slowfast_input_transform"]

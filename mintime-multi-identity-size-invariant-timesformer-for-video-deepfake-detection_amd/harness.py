@@ -8,6 +8,7 @@ from . import arch, optim, synth
 from .efficientnet import EfficientNet
 from .timesformer import SizeInvariantTimeSformer
 from .baseline import Baseline
+from . import slowfast as _slowfast
 
 
 def build_models(num_frames=8, seed=0, device="cuda", require_attention=False, drop_connect_rate=arch.DROP_CONNECT_RATE,
@@ -142,6 +143,35 @@ def baseline_train_step(ex, model, optimizer, batch, pos_weight=None, freeze_bac
 def baseline_eval_step(ex, model, batch):
     """test.py:235-244 with `--model 0`: eval forward, frame-averaged logits [B, 1]."""
     return baseline_forward(ex, model, batch)
+
+
+def build_slowfast(seed=0, device="cuda", head_pool_kernel_sizes=((8, 7, 7), (32, 7, 7)), num_classes=1):
+    """`--model 2` (train.py:143-147): slowfast_r50 with blocks[6].proj = nn.Linear(2304, num_classes), on the device, train mode.
+    Returns (model, optimizer): SGD(lr, weight_decay) of config/slowfast.yaml through optim.FusedSGD."""
+    torch.manual_seed(seed)
+    model = _slowfast.slowfast_r50(pretrained=False, head_pool_kernel_sizes=head_pool_kernel_sizes)
+    model.blocks[6].proj = torch.nn.Linear(2304, num_classes)
+    model.to(device).train()
+    opt = (optim.FusedSGD if str(device).startswith("cuda") else torch.optim.SGD)(model.parameters(), lr=0.001, weight_decay=0.0001)
+    return model, opt
+
+
+def slowfast_train_step(model, optimizer, videos, labels, pos_weight=None):
+    """One `--model 2` optimisation step (train.py:356-378): input transform, forward, BCE-with-logits, SGD.  videos [B, F, H, W, 3]
+    (uint8 or fp32), labels [B]."""
+    x = _slowfast.slowfast_input_transform(videos)
+    y_pred = model(x)
+    loss = optim.bce_with_logits(y_pred, labels, pos_weight)
+    optimizer.zero_grad(set_to_none=True)
+    loss.backward()
+    optimizer.step()
+    return loss
+
+
+@torch.no_grad()
+def slowfast_eval_step(model, videos):
+    """test.py:255-259 with `--model 2`: transform and eval forward; returns the logits."""
+    return model(_slowfast.slowfast_input_transform(videos))
 
 
 def aggregate_attentions(attentions, heads, num_frames, frames_per_identity, scale_factor=50000):

@@ -24,6 +24,12 @@ class RowMap(C.Structure):
     _fields_ = [("gin", C.c_int), ("gout", C.c_int), ("off", C.c_int)]
 
 
+class Conv3dDesc(C.Structure):
+    """mt_conv3d_desc (include/mintime_hip.h, SlowFast R50)."""
+    _fields_ = [(n, C.c_int) for n in ("N", "T", "H", "W", "C", "To", "Ho", "Wo", "K", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph",
+                                       "pw")] + [("ldx", i64), ("ldy", i64)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("op", C.c_int), ("prologue", C.c_int), ("epilogue", C.c_int),
                 ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
@@ -151,6 +157,22 @@ PROTOTYPES = {
     "mt_bn_swish_gate_planes": [f32p, f32p, f32p, f32p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "mt_baseline_head_fwd": [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [f32p] * 8 + [C.c_void_p],
     "mt_baseline_head_bwd": [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int] + [f32p] * 8 + [C.c_int, f32p, C.c_void_p],
+    "mt_conv3d_part_floats": [C.c_void_p],
+    "mt_conv3d_wgrad_splits": [C.c_void_p],
+    "mt_conv3d_fwd": [C.c_void_p, f32p, f32p, f32p, f32p, f32p, C.c_int, f32p, C.c_void_p, C.c_void_p],
+    "mt_conv3d_dgrad": [C.c_void_p, f32p, f32p, f32p, C.c_int, C.c_void_p],
+    "mt_conv3d_wgrad": [C.c_void_p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int, C.c_void_p],
+    "mt_sf_bn_relu_fwd": [f32p, i64, f32p, f32p, f32p, i64, f32p, f32p, f32p, i64, i64, C.c_int, C.c_void_p],
+    "mt_sf_bn_bwd_part_floats": [i64, C.c_int],
+    "mt_sf_bn_relu_bwd_stats": [f32p, i64, f32p, i64, f32p, f32p, f32p, i64, f32p, f32p, C.c_void_p, i64, C.c_int, C.c_void_p],
+    "mt_sf_bn_relu_bwd_apply": [f32p, i64, f32p, i64, f32p, f32p, f32p, i64, f32p, f32p, i64, C.c_int, i64, C.c_int, C.c_void_p],
+    "mt_sf_maxpool_fwd": [f32p, f32p, f32p, f32p, i64, C.c_void_p, i64, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "mt_sf_maxpool_bwd": [f32p, i64, C.c_void_p, f32p, i64, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "mt_sf_head_pool": [f32p, i64, f32p, f32p] + [C.c_int] * 10 + [C.c_void_p],
+    "mt_sf_head_proj": [f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "mt_sf_head_bwd": [f32p] * 7 + [C.c_int] * 4 + [C.c_void_p],
+    "mt_sf_head_dfeat": [f32p, f32p, i64] + [C.c_int] * 10 + [C.c_void_p],
+    "mt_sf_ingest": [C.c_void_p, C.c_int, i64, i64, i64, i64, i64, C.c_void_p] + [C.c_int] * 6 + [f32p, f32p, C.c_void_p],
     "mt_plan_create": [C.POINTER(C.c_void_p)],
     "mt_plan_destroy": [C.c_void_p],
     "mt_plan_record_begin": [C.c_void_p],
@@ -163,7 +185,8 @@ PROTOTYPES = {
     "mt_memset_async": [C.c_void_p, C.c_int, i64, C.c_void_p],
     "mt_copy_async": [C.c_void_p, C.c_void_p, i64, C.c_void_p],
 }
-_RESTYPES = {"mt_last_error": C.c_char_p, "mt_planes_elems": C.c_int64, "mt_gemm_planes_workspace_bytes": C.c_int64}
+_RESTYPES = {"mt_last_error": C.c_char_p, "mt_planes_elems": C.c_int64, "mt_gemm_planes_workspace_bytes": C.c_int64,
+             "mt_conv3d_part_floats": C.c_int64, "mt_sf_bn_bwd_part_floats": C.c_int64}
 
 
 class MintimeHipError(RuntimeError):
@@ -185,7 +208,7 @@ def build(verbose: bool = False):
 
 # MT_VERSION of include/mintime_hip.h this binding was written against (tests/test_host_logic.py keeps the two equal; the package
 # itself does not need the header at run time -- it may be copied or installed without the repository's include/ directory)
-ABI_VERSION = 120
+ABI_VERSION = 121
 
 
 def header_version() -> int:

@@ -1,0 +1,251 @@
+"""SlowFast R50 (reference train.py:143-147 / test.py:121-125, `--model 2`) on libmintime_hip (MI355X).
+
+The reference loads pytorchvideo's `slowfast_r50` from the network and replaces its classifier:
+
+    model = torch.hub.load('facebookresearch/pytorchvideo', 'slowfast_r50', pretrained=True)
+    model.blocks[6].proj = torch.nn.Linear(2304, 1)
+
+`slowfast_r50()` builds the same network from its published structure (pytorchvideo `create_slowfast`: depth 50, alpha 4, beta 1/8,
+fusion kernel (7, 1, 1)) with pytorchvideo's module names, so the state-dict keys and shapes are pytorchvideo's
+(tests/golden/slowfast_r50_manifest.json, written by hand from that structure: it has not been checked against pytorchvideo itself).
+The modules only hold parameters and settings; `SlowFast.forward` runs the whole network in the HIP library (slowfast_engine.py).
+
+Inputs: `forward([slow, fast])` with slow [B, 3, 8, H, W] and fast [B, 3, 32, H, W] (the reference's PackPathway output), or the pair
+`slowfast_input_transform(videos)` returns (device tensors that the network reads without a copy).
+"""
+import torch
+from torch import nn
+
+from . import lib as L
+
+SLOW_INNER = (64, 128, 256, 512)
+SLOW_OUT = (256, 512, 1024, 2048)
+FAST_INNER = (8, 16, 32, 64)
+FAST_OUT = (32, 64, 128, 256)
+DEPTHS = (3, 4, 6, 3)
+SLOW_CONV_A_T = (1, 1, 3, 3)
+FAST_CONV_A_T = (3, 3, 3, 3)
+STAGE_STRIDE = (1, 2, 2, 2)
+STEM_OUT = (64, 8)
+FUSION_KERNEL, FUSION_STRIDE, FUSION_RATIO = 7, 4, 2
+ALPHA = 4                                   # fast frames per slow frame (PackPathway)
+HEAD_DIM = SLOW_OUT[-1] + FAST_OUT[-1]      # 2304
+NUM_FRAMES = 32                             # UniformTemporalSubsample(32) of utils.py:166
+
+
+class _Stem(nn.Module):
+    def __init__(self, cout, kt):
+        super().__init__()
+        self.conv = nn.Conv3d(3, cout, (kt, 7, 7), stride=(1, 2, 2), padding=(kt // 2, 3, 3), bias=False)
+        self.norm = nn.BatchNorm3d(cout, eps=1e-5, momentum=0.1)
+        self.activation = nn.ReLU()
+        self.pool = nn.MaxPool3d((1, 3, 3), stride=(1, 2, 2), padding=(0, 1, 1))
+
+
+class _Fusion(nn.Module):
+    def __init__(self, cfast):
+        super().__init__()
+        cout = FUSION_RATIO * cfast
+        self.conv_fast_to_slow = nn.Conv3d(cfast, cout, (FUSION_KERNEL, 1, 1), stride=(FUSION_STRIDE, 1, 1),
+                                           padding=(FUSION_KERNEL // 2, 0, 0), bias=False)
+        self.norm = nn.BatchNorm3d(cout, eps=1e-5, momentum=0.1)
+        self.activation = nn.ReLU()
+
+
+class _Branch2(nn.Module):
+    def __init__(self, cin, inner, cout, kt, stride):
+        super().__init__()
+        self.conv_a = nn.Conv3d(cin, inner, (kt, 1, 1), padding=(kt // 2, 0, 0), bias=False)
+        self.norm_a = nn.BatchNorm3d(inner, eps=1e-5, momentum=0.1)
+        self.act_a = nn.ReLU()
+        self.conv_b = nn.Conv3d(inner, inner, (1, 3, 3), stride=(1, stride, stride), padding=(0, 1, 1), bias=False)
+        self.norm_b = nn.BatchNorm3d(inner, eps=1e-5, momentum=0.1)
+        self.act_b = nn.ReLU()
+        self.conv_c = nn.Conv3d(inner, cout, 1, bias=False)
+        self.norm_c = nn.BatchNorm3d(cout, eps=1e-5, momentum=0.1)
+        self.norm_c.block_final_bn = True
+
+
+class _ResBlock(nn.Module):
+    def __init__(self, cin, inner, cout, kt, stride):
+        super().__init__()
+        if cin != cout or stride != 1:
+            self.branch1_conv = nn.Conv3d(cin, cout, 1, stride=(1, stride, stride), bias=False)
+            self.branch1_norm = nn.BatchNorm3d(cout, eps=1e-5, momentum=0.1)
+        else:
+            self.branch1_conv = None
+            self.branch1_norm = None
+        self.branch2 = _Branch2(cin, inner, cout, kt, stride)
+        self.activation = nn.ReLU()
+
+
+class _ResStage(nn.Module):
+    def __init__(self, cin, inner, cout, kt, stride, depth):
+        super().__init__()
+        self.res_blocks = nn.ModuleList(
+            [_ResBlock(cin if i == 0 else cout, inner, cout, kt, stride if i == 0 else 1) for i in range(depth)])
+
+
+class _MultiPathway(nn.Module):
+    def __init__(self, pathways, fusion):
+        super().__init__()
+        self.multipathway_blocks = nn.ModuleList(pathways)
+        self.multipathway_fusion = fusion
+
+
+class _PoolConcat(nn.Module):
+    def __init__(self, kernel_sizes):
+        super().__init__()
+        self.pool = nn.ModuleList([nn.AvgPool3d(tuple(k), stride=(1, 1, 1), padding=(0, 0, 0)) for k in kernel_sizes])
+        self.dim = 1
+
+
+class _Head(nn.Module):
+    def __init__(self, dim, num_classes, dropout):
+        super().__init__()
+        self.dropout = nn.Dropout(dropout)
+        self.proj = nn.Linear(dim, num_classes)
+        self.output_pool = nn.AdaptiveAvgPool3d(1)
+
+
+class SlowFast(nn.Module):
+    """pytorchvideo's `Net` of slowfast_r50: `blocks[0]` stems + fusion, `blocks[1..4]` res stages (+ fusion for 1..3), `blocks[5]`
+    pooling + concat, `blocks[6]` head.  `blocks[6].proj` may be replaced by any nn.Linear(2304, k): the head reads it at call time."""
+
+    def __init__(self, head_pool_kernel_sizes=((8, 7, 7), (32, 7, 7)), num_classes=400, dropout_rate=0.5):
+        super().__init__()
+        blocks = [_MultiPathway([_Stem(STEM_OUT[0], 1), _Stem(STEM_OUT[1], 5)], _Fusion(STEM_OUT[1]))]
+        slow_in = STEM_OUT[0] + FUSION_RATIO * STEM_OUT[1]
+        fast_in = STEM_OUT[1]
+        for s in range(4):
+            slow = _ResStage(slow_in, SLOW_INNER[s], SLOW_OUT[s], SLOW_CONV_A_T[s], STAGE_STRIDE[s], DEPTHS[s])
+            fast = _ResStage(fast_in, FAST_INNER[s], FAST_OUT[s], FAST_CONV_A_T[s], STAGE_STRIDE[s], DEPTHS[s])
+            fusion = _Fusion(FAST_OUT[s]) if s < 3 else None
+            blocks.append(_MultiPathway([slow, fast], fusion))
+            slow_in = SLOW_OUT[s] + (FUSION_RATIO * FAST_OUT[s] if s < 3 else 0)
+            fast_in = FAST_OUT[s]
+        blocks.append(_PoolConcat(head_pool_kernel_sizes))
+        blocks.append(_Head(HEAD_DIM, num_classes, dropout_rate))
+        self.blocks = nn.ModuleList(blocks)
+        self.head_pool_kernel_sizes = tuple(tuple(int(v) for v in k) for k in head_pool_kernel_sizes)
+        # dropout draws: torch.rand unless set to fn(shape, device) -> uniforms of `shape` (shape = the pooled [B, 2304, Pt, Ph, Pw])
+        self.dropout_uniform = None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        """pytorchvideo's init_net_weights(style="resnet"): convolutions c2_msra_fill, BatchNorm weight 1 (0 for the last one of every
+        bottleneck), bias 0; the projection normal(0, 0.01) with zero bias."""
+        for m in self.modules():
+            if isinstance(m, nn.Conv3d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(m, nn.BatchNorm3d):
+                nn.init.constant_(m.weight, 0.0 if getattr(m, "block_final_bn", False) else 1.0)
+                nn.init.zeros_(m.bias)
+            elif isinstance(m, nn.Linear):
+                nn.init.normal_(m.weight, std=0.01)
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """Accepts pytorchvideo checkpoints, also as saved from an nn.DataParallel wrap (`module.` prefix)."""
+        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+        return super().load_state_dict(sd, strict=strict, **kw)
+
+    def forward(self, x):
+        from . import slowfast_engine
+        return slowfast_engine.slowfast_apply(self, x)
+
+
+def slowfast_r50(pretrained=False, weights_path=None, head_pool_kernel_sizes=((8, 7, 7), (32, 7, 7)), **kwargs):
+    """torch.hub entry point with pytorchvideo's signature.  `pretrained=True` needs a local `weights_path` (a pytorchvideo state dict,
+    e.g. SLOWFAST_8x8_R50.pyth's "model_state"): the Kinetics checkpoint is not fetched from the network."""
+    model = SlowFast(head_pool_kernel_sizes=head_pool_kernel_sizes, **kwargs)
+    if pretrained and weights_path is None:
+        raise RuntimeError("slowfast_r50(pretrained=True) downloads the Kinetics-400 checkpoint, which needs network access; pass "
+                           "weights_path=<local pytorchvideo state dict> instead")
+    if weights_path is not None:
+        sd = torch.load(weights_path, map_location="cpu")
+        if isinstance(sd, dict) and "model_state" in sd:
+            sd = sd["model_state"]
+        model.load_state_dict(sd)
+    return model
+
+
+# ---- input transform (reference utils.py:140-186) -------------------------------------------------------------------------------
+
+def frame_indices(n_in, n_out):
+    """`torch.linspace(0, n_in - 1, n_out).long()` (UniformTemporalSubsample, PackPathway) in integer arithmetic."""
+    if n_out == 1:
+        return [0]
+    return [(i * (n_in - 1)) // (n_out - 1) for i in range(n_out)]
+
+
+def _packed_view(buf):
+    """[B, T, H, W, 4] packed buffer -> the [B, 3, T, H, W] tensor the reference's transform returns (a view, no copy)."""
+    v = buf[..., :3].permute(0, 4, 1, 2, 3)
+    v._mt_packed = buf
+    return v
+
+
+def ingest(src, fidx, normalize, layout, split=None):
+    """One mt_sf_ingest launch: frames fidx of src (uint8 or fp32; layout 'bfhwc' or 'bcfhw') -> packed [B, T, H, W, 4] buffers: one
+    of len(fidx) frames, or two (the first `split` frames, then the rest) when split is given."""
+    if layout == "bfhwc":
+        B, F, H, W, _ = src.shape
+        sb, sf, sh, sw, sc = src.stride()
+    else:
+        B, _, F, H, W = src.shape
+        sb, sc, sf, sh, sw = src.stride()
+    if max(fidx) >= F:
+        raise ValueError(f"frame index {max(fidx)} out of range for {F} frames")
+    is_u8 = src.dtype == torch.uint8
+    if not is_u8 and src.dtype != torch.float32:
+        src = src.float()
+        sb, sf, sh, sw, sc = [src.stride(i) for i in ((0, 1, 2, 3, 4) if layout == "bfhwc" else (0, 2, 3, 4, 1))]
+    n = len(fidx)
+    split = n if split is None else split
+    out = torch.empty(B, split, H, W, 4, dtype=torch.float32, device=src.device)
+    out2 = torch.empty(B, n - split, H, W, 4, dtype=torch.float32, device=src.device) if split < n else None
+    idx = torch.tensor(fidx, dtype=torch.int32).to(src.device)
+    L.check(L.get().mt_sf_ingest(L.ptr(src), int(is_u8), sb, sf, sh, sw, sc, L.ptr(idx), n, split, B, H, W, int(normalize), L.ptr(out),
+                                 L.ptr(out2), L.stream_ptr()), "mt_sf_ingest")
+    return out if out2 is None else (out, out2)
+
+
+def slowfast_input_transform(videos, crop_size=256, side_size=256, num_frames=NUM_FRAMES, device=None):
+    """utils.py:166-186 for a batch: `videos` [B, F, H, W, 3] (the loader's layout) or [B, 3, F, H, W] (after train.py:357's
+    rearrange), uint8 or fp32.  Returns [slow [B, 3, 8, H, W], fast [B, 3, 32, H, W]] on the device, as train.py:358 builds them:
+    UniformTemporalSubsample(32), /255, Normalize(0.45, 0.225), PackPathway.  ShortSideScale(256) and CenterCrop(256) are identities
+    at the configured 256 x 256 (config/slowfast.yaml); other sizes are not supported."""
+    if not torch.is_tensor(videos) or videos.dim() != 5:
+        raise ValueError("slowfast_input_transform: expected a [B, F, H, W, 3] or [B, 3, F, H, W] tensor")
+    layout = "bfhwc" if videos.shape[-1] == 3 else "bcfhw"
+    if layout == "bcfhw" and videos.shape[1] != 3:
+        raise ValueError(f"slowfast_input_transform: no 3-channel axis in {tuple(videos.shape)}")
+    H, W = (videos.shape[2], videos.shape[3]) if layout == "bfhwc" else (videos.shape[3], videos.shape[4])
+    if not (H == W == crop_size == side_size):
+        raise NotImplementedError(f"slowfast_input_transform: ShortSideScale({side_size}) + CenterCrop({crop_size}) are only the identity "
+                                  f"for {side_size} x {side_size} frames (config/slowfast.yaml); got {H} x {W} -- the resize is not "
+                                  "implemented")
+    if not videos.is_cuda:
+        videos = videos.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+    F = videos.shape[1] if layout == "bfhwc" else videos.shape[2]
+    fi = frame_indices(F, num_frames)
+    si = frame_indices(num_frames, num_frames // ALPHA)
+    slow, fast = ingest(videos, [fi[j] for j in si] + fi, True, layout, split=len(si))
+    return [_packed_view(slow), _packed_view(fast)]
+
+
+def pack_pathway_input(x):
+    """A pathway input [B, 3, T, H, W] -> packed [B, T, H, W, 4] (no copy when it came from slowfast_input_transform)."""
+    buf = getattr(x, "_mt_packed", None)
+    if buf is not None and buf.is_cuda:
+        return buf
+    if not x.is_cuda:
+        raise L.MintimeHipError("SlowFast (MI355X build) needs device tensors; there is no CPU path")
+    if x.dim() != 5 or x.shape[1] != 3:
+        raise ValueError(f"expected a [B, 3, T, H, W] pathway input, got {tuple(x.shape)}")
+    return ingest(x.detach(), list(range(x.shape[2])), False, "bcfhw")
+
+
+__all__ = ["SlowFast", "slowfast_r50", "slowfast_input_transform", "frame_indices"]
