@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from . import lib as L
+from . import plans
 from .timesformer import _Linear, _Seq
 
 # what the last backward launched (tests: frozen parameters and an input without gradient cost nothing)
@@ -47,11 +48,6 @@ class Baseline(nn.Module):
         return baseline_apply(self, x)
 
 
-def _stamp(params):
-    from .tsf_planes import WEIGHT_EPOCH          # bumped by the fused optimizers, which update parameters through raw pointers
-    return tuple(p._version for p in params), tuple(p.data_ptr() for p in params), WEIGHT_EPOCH[0]
-
-
 class _BaselineHeadFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, mode, x, w1, b1, w2, b2):
@@ -68,18 +64,15 @@ class _BaselineHeadFunction(torch.autograd.Function):
         L.check(L.get().mt_baseline_head_fwd(L.ptr(x), layout, n, hw, C, m, L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), L.ptr(vc),
                                              L.ptr(pooled), L.ptr(part), L.ptr(logits), L.stream_ptr()), "mt_baseline_head_fwd")
         ctx.model, ctx.dims, ctx.params, ctx.x_shape = model, (layout, n, hw, C, m), (w1, b1, w2, b2), x.shape
-        ctx.saved = dict(pooled=pooled, vc=vc, stamp=_stamp((w1, b1, w2, b2))) if save else None
+        ctx.saved = dict(pooled=pooled, vc=vc, stamp=plans.stamp((w1, b1, w2, b2))) if save else None
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         if ctx.saved is None:
-            raise RuntimeError("Baseline: backward ran a second time through the same forward; the saved buffers are released after the "
-                               "first pass (retain_graph is not supported by the HIP engine)")
+            plans.refuse_second_pass("Baseline")
         w1, b1, w2, b2 = ctx.params
-        if _stamp(ctx.params) != ctx.saved["stamp"]:
-            raise RuntimeError("Baseline: the head weights were updated between this graph's forward and its backward (v = W1^T w2 was "
-                               "formed from the old values): run backward before the optimizer step")
+        plans.check_stamp(ctx.params, ctx.saved["stamp"], "Baseline", "the head weights", "v = W1^T w2 was formed from the old values")
         layout, n, hw, C, m = ctx.dims
         need_x = ctx.needs_input_grad[2]
         need_p = ctx.needs_input_grad[3:7]

@@ -337,7 +337,7 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
                                   "(train.py never sets requires_grad on videos)")
     LAST_RUN.update(run)
     if plan is not None:
-        plan.extra["flat_grads"] = flat_grads
+        plan.extra.update(flat_grads=flat_grads, last_run=dict(LAST_RUN))       # (a replay restores LAST_RUN)
     L.grads_ready(model, params, flat_grads)
     out = [g if nd else None for nd, g in zip(need_dparams, grads)]
     return None, out

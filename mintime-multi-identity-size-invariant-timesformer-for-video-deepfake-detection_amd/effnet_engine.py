@@ -6,6 +6,7 @@ import torch
 
 from . import arch
 from . import lib as L
+from . import plans
 
 SLOTS = 32   # replicated fp64 BatchNorm accumulators (spreads atomic traffic)
 STEM_DIRECT = __import__("os").environ.get("MT_STEM_DIRECT", "1") != "0"    # 0 = the im2col-prologue GEMM
@@ -103,7 +104,8 @@ def planes_scope(model, N):
 
 def weight_planes(model, params, exp, proj, head):
     """Plane tensors of the 1x1-conv weights that run on plane operands, re-split from the fp32 weights by ONE launch per forward
-    (mt_split_planes_blk_multi; cf. tsf_planes.weight_planes).  Returns {("e", block) | ("p", block) | "head": planes}."""
+    (mt_split_planes_blk_multi; cf. tsf_planes.weight_planes).  Returns ({("e", block) | ("p", block) | "head": planes}, the saved
+    serial of their holder or None)."""
     lib = L.get()
     blocks = model._blocks
     sel, pos = [], 3
@@ -118,7 +120,7 @@ def weight_planes(model, params, exp, proj, head):
     if head:
         sel.append(("head", params[pos], arch.HEAD_COUT, arch.HEAD_CIN))
     if not sel:
-        return {}
+        return {}, None
     # one cache entry per (weight storage, selection): another batch size selects other convolutions, and a recorded launch plan
     # (plans.py) keeps reading the table and the plane tensors of the entry it was recorded with
     ident = tuple((k, w.data_ptr()) for k, w, _, _ in sel)
@@ -137,35 +139,11 @@ def weight_planes(model, params, exp, proj, head):
             rows.append((w.data_ptr(), t.data_ptr(), r, c, first))
             first += t.shape[1] * t.shape[2]
         host = torch.tensor(rows, dtype=torch.int64).pin_memory()
-        cache = caches[ident] = dict(holder=holder, host=host, table=host.to(dev, non_blocking=True), blocks=first, count=len(rows))
+        cache = caches[ident] = dict(holder=holder, host=host, table=host.to(dev, non_blocking=True), blocks=first, count=len(rows),
+                                     serial=plans.PlaneSerial("the 1x1-conv weights"))
     L.check(lib.mt_split_planes_blk_multi(L.ptr(cache["table"]), cache["count"], cache["blocks"], L.stream_ptr()),
             "mt_split_planes_blk_multi")       # (L.ptr: a plan being recorded pins the table)
-    weight_planes_touch(model, cache, [w for _, w, _, _ in sel])
-    return cache["holder"]
-
-
-def weight_planes_touch(model, cache=None, ws=None):
-    """A new serial when the weights changed since the planes were last written (cf. tsf_planes.weight_planes): graphs that saved
-    an older serial must not run their backward on the re-split planes.  A replayed forward (the split launch is in the plan)
-    calls this with no arguments for the bookkeeping alone.  Returns the serial the forward's planes carry, None without planes."""
-    from .tsf_planes import WEIGHT_EPOCH
-    st = model.__dict__.setdefault("_ef_wplanes_state", dict(serial=0, stamp=None, ws=None))
-    if ws is not None:
-        st["ws"], st["ident"] = ws, id(cache)
-    if st["ws"] is None:
-        return None
-    stamp = (tuple(w._version for w in st["ws"]), tuple(w.data_ptr() for w in st["ws"]), st["ident"], WEIGHT_EPOCH[0])
-    if stamp != st["stamp"]:
-        st["serial"] += 1
-        st["stamp"] = stamp
-    return st["serial"]
-
-
-def check_weight_serial(model, saved):
-    ser = saved.get("w_serial")
-    if ser is not None and model.__dict__.get("_ef_wplanes_state", {}).get("serial") != ser:
-        raise RuntimeError("EfficientNet: the 1x1-conv weights were updated between this graph's forward and its backward (their "
-                           "operand planes were rewritten by a later forward): run backward before the optimizer step")
+    return cache["holder"], cache["serial"].touch([w for _, w, _, _ in sel])
 
 
 def _bump_tracked(plan=None):
@@ -217,7 +195,7 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
     sptr = (lambda b_: L.ptr(b_.stats)) if training else (lambda b_: None)
     saved = {"blocks": []} if save else None
     pl_exp, pl_proj, pl_head = planes_scope(model, N)
-    wpl = weight_planes(model, params, pl_exp, pl_proj, pl_head)
+    wpl, w_serial = weight_planes(model, params, pl_exp, pl_proj, pl_head)
     y_p = None                   # planes of the current block input y (written by the producing block's bn_act when the next conv wants them)
 
     # ---- stem
@@ -353,117 +331,49 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
                               st), "mt_bn_act_fwd")
     if save:
         saved["head"] = dict(y_in=y, z=z_h, bn=bn_h, y_p=y_p if pl_head else None, w_p=wpl.get("head"))
-        saved["w_serial"] = model.__dict__.get("_ef_wplanes_state", {}).get("serial") if wpl else None
+        saved["w_serial"] = w_serial
     _bump_tracked(plan)
     return feat, saved, ys
-
-
-def _state_tensors(model, params):
-    """Everything a recorded phase holds an address of besides its own buffers: parameters and BatchNorm buffers."""
-    return list(params) + [b for b in model.buffers()]
 
 
 class _EffNetFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, want_blocks, x_nhwc, *params):
-        from . import plans
         want_blocks, grad_on = want_blocks
         save = grad_on and any(ctx.needs_input_grad)      # see tsf_engine._TSFFunction.forward
         N, H, W, _ = x_nhwc.shape
         ctx.shape = (N, H, W)
         ctx.model, ctx.params, ctx.training = model, params, model.training
-        ctx.plan = ctx.token = None
-        np_, mode = None, "eager"
+        stream = key = state = None
         if save and not want_blocks:
             stream = torch.cuda.current_stream(x_nhwc.device).cuda_stream
+            state = list(params) + list(model.buffers())       # (what a recording holds the addresses of)
             key = ("ef", tuple(x_nhwc.shape), x_nhwc.dtype, model.training, L.deterministic(), L.gemm_split_enabled(),
                    float(model.drop_connect_rate), tuple(ctx.needs_input_grad[3:]), stream,
                    float(model._bn0.momentum), float(model._bn0.eps))       # (scalars a recorded call holds by value)
-            np_, mode = plans.lookup(model, key)
-            if mode == "replay" and np_.state_ptrs != plans.state_ptrs(_state_tensors(model, params)):
-                plans.drop(model, np_)                   # parameters / buffers moved (load_state_dict, .to()): record afresh later
-                np_, mode = None, "eager"
-        if mode == "eager":
-            feat, saved, ys = effnet_forward(model, x_nhwc, params, model.training, save, want_blocks)
-            ctx.saved = saved
-            outs = [feat]
-            if want_blocks:
-                for t in ys:
-                    ctx.mark_non_differentiable(t)
-                outs += ys
-            return tuple(outs)
-        if mode == "record":
-            np_.stream = stream
-            x_s = plans.static_input(np_, "x", x_nhwc)
-            pl = L.Plan()
-            try:
-                with pl:
-                    feat, saved, _ = effnet_forward(model, x_s, params, model.training, True, False, plan=np_)
-            except Exception:
-                np_.broken = True
-                raise
-            np_.fwd = pl
-            np_.extra.update(saved=saved, feat=feat)
-            np_.state_ptrs = plans.state_ptrs(_state_tensors(model, params))
-            plans.own(np_, feat)
-            plans.STATS["recorded"] += 1
-        else:
-            plans.refresh_input(np_, "x", x_nhwc)
+
+        def body(ins, plan):
+            feat, saved, ys = effnet_forward(model, ins["x"], params, model.training, save, want_blocks, plan=plan)
+            for t in ys or ():
+                ctx.mark_non_differentiable(t)
+            return (feat, *(ys or ())), saved
+
+        def gates(np_):      # this step's drop-connect draws into the recorded gate buffer
             if np_.extra.get("gates") is not None:
                 np_.extra["gates"].copy_(_dc_gates(model, N, x_nhwc.device)[1])
-            plans.run(np_.fwd)
-            if np_.extra["saved"].get("w_serial") is not None:
-                np_.extra["saved"]["w_serial"] = weight_planes_touch(model)       # the split launch is in the plan
-            if np_.extra.get("tracked"):
-                torch._foreach_add_(np_.extra["tracked"], 1)
-        ctx.plan, ctx.token = np_, np_.begin()
-        ctx.saved = np_.extra["saved"]
-        return (np_.extra["feat"].detach(),)
+        return plans.forward(ctx, model, key, stream, state, {"x": x_nhwc}, body, before_run=gates)
 
     @staticmethod
     def backward(ctx, dfeat, *unused):
-        if ctx.saved is None:
-            raise RuntimeError("EfficientNet: backward ran a second time through the same forward; the activation buffers are "
-                               "released after the first pass (retain_graph is not supported by the HIP engine)")
-        from . import plans
         from .effnet_backward import effnet_backward, LAST_RUN
-        np_ = ctx.plan
-        check_weight_serial(ctx.model, ctx.saved)
-        dfeat = dfeat.contiguous()
         need_dx, need_dp = ctx.needs_input_grad[2], ctx.needs_input_grad[3:]
-        if np_ is None:
-            dx, dparams = effnet_backward(ctx.model, ctx.params, ctx.saved, ctx.shape, ctx.training, dfeat, need_dx, need_dp)
-        elif (plans.grads_exist(ctx.params) or torch.cuda.current_stream(dfeat.device).cuda_stream != np_.stream
-              or torch.cuda.is_current_stream_capturing()):
-            # gradients that already exist are ADDED to by autograd: they alias the plan's gradient buffer, so this pass needs
-            # fresh ones -- the eager launch sequence over the plan's saved activations (which stay for the next replay)
-            plans.STATS["eager_accumulate"] += 1
-            dx, dparams = effnet_backward(ctx.model, ctx.params, ctx.saved, ctx.shape, ctx.training, dfeat, need_dx, need_dp,
-                                          keep_saved=True)
-        elif np_.bwd is None:
-            d_s = plans.static_input(np_, "dfeat", dfeat)
-            pl = L.Plan()
-            try:
-                with pl:
-                    dx, dparams = effnet_backward(ctx.model, ctx.params, ctx.saved, ctx.shape, ctx.training, d_s, need_dx, need_dp,
-                                                  keep_saved=True, plan=np_)
-            except Exception:
-                np_.broken = True
-                raise
-            np_.bwd = pl
-            np_.extra.update(grads=list(dparams), last_run=dict(LAST_RUN))
-            dparams = plans.fresh_aliases(dparams)
-        else:
-            plans.refresh_input(np_, "dfeat", dfeat)
-            plans.run(np_.bwd)
-            LAST_RUN.update(np_.extra["last_run"])
-            L.grads_ready(ctx.model, ctx.params, np_.extra["flat_grads"])
-            dx, dparams = None, plans.fresh_aliases(np_.extra["grads"])
-        ctx.saved = None
-        if np_ is not None:
-            np_.release(ctx.token)
-            ctx.token = None
-        return (None, None, dx) + tuple(dparams)
+
+        def body(g, keep_saved, plan):
+            dx, dparams = effnet_backward(ctx.model, ctx.params, ctx.saved, ctx.shape, ctx.training, g, need_dx, need_dp,
+                                          keep_saved=keep_saved, plan=plan)
+            return (dx,), dparams
+        return (None, None) + plans.backward(ctx, "EfficientNet", dfeat.contiguous(), body,
+                                             after_run=lambda np_: LAST_RUN.update(np_.extra["last_run"]))
 
 
 def effnet_apply(model, inputs, want_blocks=False):

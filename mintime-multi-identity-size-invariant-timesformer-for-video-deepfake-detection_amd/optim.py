@@ -4,14 +4,14 @@ the device together with its gradient."""
 import torch
 
 from . import lib as L
+from . import plans
 
 _CHUNK = 4096
 
 
 def _weights_changed():
     """Parameters were updated through raw pointers (torch's version counters did not move): cached operand planes are stale."""
-    from . import tsf_planes
-    tsf_planes.WEIGHT_EPOCH[0] += 1
+    plans.WEIGHT_EPOCH[0] += 1
 
 
 class FusedSGD(torch.optim.Optimizer):

@@ -33,6 +33,8 @@ OWNED = set()                 # storage addresses of plan-owned output buffers (
 ALL = weakref.WeakSet()       # live NetPlans (bench.py reads their probes)
 PROBE_MASK = [0]              # bit t: time the calls tagged t (lib.TAG_*) inside mt_plan_run
 STATS = {"recorded": 0, "replayed": 0, "eager_in_flight": 0, "eager_accumulate": 0, "dropped": 0}
+# bumped by the fused optimizers (optim.py): they update parameters through raw pointers, which torch's version counters do not see
+WEIGHT_EPOCH = [0]
 
 
 class _Token:
@@ -176,6 +178,150 @@ def grads_exist(params):
 def fresh_aliases(views):
     """New tensor objects over the plan's gradient buffer: autograd adopts a gradient it holds the only reference to (no copy)."""
     return [None if v is None else v.detach() for v in views]
+
+
+def forward(ctx, model, key, stream, state, inputs, body, clone_outputs=False, before_run=None, after_run=None):
+    """Forward of a phase that may run from a launch plan; sets ctx.plan / ctx.token / ctx.saved and returns the outputs.
+    key: None when the call is not plannable (it runs eagerly); stream: the current stream (part of the key).
+    state: the tensors besides its own buffers whose addresses a recording holds -- a replay after any of them moved drops the plan.
+    inputs: {name: tensor} the phase reads; a recording reads them from static buffers, a replay refreshes those.
+    body(inputs, plan) -> (outputs, saved): the engine's launch sequence; plan is the NetPlan being recorded, or None.
+    before_run / after_run(np_): a replay's per-step work besides the recorded launches.
+    A plan's outputs are static buffers: handed out as fresh aliases, or as copies with clone_outputs."""
+    ctx.plan = ctx.token = None
+    np_, mode = (None, "eager") if key is None else lookup(model, key)
+    if mode == "replay" and np_.state_ptrs != state_ptrs(state):
+        drop(model, np_)                   # parameters / buffers moved (load_state_dict, .to()): record afresh later
+        np_, mode = None, "eager"
+    if mode == "eager":
+        outs, ctx.saved = body(inputs, None)
+        return outs
+    if mode == "record":
+        np_.stream = stream
+        statics = {name: static_input(np_, name, t) for name, t in inputs.items()}
+        pl = L.Plan()
+        try:
+            with pl:
+                outs, saved = body(statics, np_)
+        except Exception:
+            np_.broken = True
+            raise
+        np_.fwd = pl
+        np_.extra.update(saved=saved, outs=outs)
+        np_.state_ptrs = state_ptrs(state)
+        own(np_, outs[0])
+        STATS["recorded"] += 1
+    else:
+        for name, t in inputs.items():
+            refresh_input(np_, name, t)
+        if before_run is not None:
+            before_run(np_)
+        run(np_.fwd)
+        saved = np_.extra["saved"]
+        if saved.get("w_serial") is not None:
+            saved["w_serial"] = saved["w_serial"][0].touch()      # the split launch is in the plan
+        if np_.extra.get("tracked"):
+            torch._foreach_add_(np_.extra["tracked"], 1)          # BatchNorm num_batches_tracked (effnet_engine._bump_tracked)
+        if after_run is not None:
+            after_run(np_)
+    ctx.plan, ctx.token, ctx.saved = np_, np_.begin(), np_.extra["saved"]
+    return tuple(None if t is None else t.clone() if clone_outputs else t.detach() for t in np_.extra["outs"])
+
+
+def backward(ctx, net, grad, body, after_run=None):
+    """Backward of a phase forward() ran; returns (input gradients..., parameter gradients...).
+    net: the network's name in error messages; grad: the gradient of the phase's output (contiguous).
+    body(grad, keep_saved, plan) -> (input gradients, parameter gradients): the engine's reverse launch sequence over ctx.saved;
+    keep_saved: the activations belong to a plan and stay for its next replay.  after_run(np_): a replay's host-side bookkeeping."""
+    if ctx.saved is None:
+        refuse_second_pass(net)
+    check_planes(ctx.saved, net)
+    np_ = ctx.plan
+    if np_ is None:
+        dins, dparams = body(grad, False, None)
+    elif (grads_exist(ctx.params) or torch.cuda.current_stream(grad.device).cuda_stream != np_.stream
+          or torch.cuda.is_current_stream_capturing()):
+        # gradients that already exist are ADDED to by autograd: they alias the plan's gradient buffer, so this pass needs fresh
+        # ones -- the eager launch sequence over the plan's saved activations (which stay for the next replay)
+        STATS["eager_accumulate"] += 1
+        dins, dparams = body(grad, True, None)
+    elif np_.bwd is None:
+        g = static_input(np_, "grad", grad)
+        pl = L.Plan()
+        try:
+            with pl:
+                dins, dparams = body(g, True, np_)
+        except Exception:
+            np_.broken = True
+            raise
+        np_.bwd = pl
+        np_.extra.update(dins=dins, grads=list(dparams))
+        own(np_, *dins)
+        dins, dparams = fresh_aliases(dins), fresh_aliases(dparams)
+    else:
+        refresh_input(np_, "grad", grad)
+        run(np_.bwd)
+        if after_run is not None:
+            after_run(np_)
+        L.grads_ready(ctx.model, ctx.params, np_.extra["flat_grads"])
+        dins, dparams = fresh_aliases(np_.extra["dins"]), fresh_aliases(np_.extra["grads"])
+    ctx.saved = None
+    if np_ is not None:
+        np_.release(ctx.token)
+        ctx.token = None
+    return tuple(dins) + tuple(dparams)
+
+
+# ---- stale weights: a backward must not run on values derived from weights that changed after its forward
+
+def stamp(tensors):
+    """What a value derived from `tensors` depends on: their version counters, their storage, and WEIGHT_EPOCH."""
+    return (WEIGHT_EPOCH[0], *[(t._version, t.data_ptr()) for t in tensors])
+
+
+class PlaneSerial:
+    """Serial of one holder of persistent weight planes (re-split from the fp32 weights by every forward).  It moves when a split
+    writes the planes from weights whose stamp differs from the previous split's: a graph that saved an older serial would run its
+    backward on planes of other weights.  Nothing else moves it -- not which selection or batch size made the call, nor a holder
+    that grew (weights appended, the earlier ones unchanged: no plane an earlier forward read was written with other values)."""
+    __slots__ = ("what", "value", "stamp", "weights")
+
+    def __init__(self, what):
+        self.what, self.value, self.stamp, self.weights = what, 0, (), ()
+
+    def touch(self, weights=None):
+        """The planes were just split from `weights` (None: the same tensors as last time -- a replayed forward, whose split launch
+        is part of the recording).  Returns what a forward saves as saved["w_serial"] (backward() checks it)."""
+        if weights is not None:
+            self.weights = weights
+        s = stamp(self.weights)
+        if s[:len(self.stamp)] != self.stamp:
+            self.value += 1
+        self.stamp = s
+        return self, self.value
+
+
+def check_planes(saved, net):
+    """Persistent plane holders: refuse when the planes this backward reads were re-split from other weights after its forward."""
+    ws = saved.get("w_serial")
+    if ws is not None and ws[0].value != ws[1]:
+        refuse_updated(net, ws[0].what, "their operand planes were rewritten by a later forward")
+
+
+def check_stamp(tensors, taken, net, what, why=None):
+    """Per-forward derived values: refuse when the stamp of `tensors` differs from the one the forward took."""
+    if stamp(tensors) != taken:
+        refuse_updated(net, what, why)
+
+
+def refuse_second_pass(net):
+    raise RuntimeError(f"{net}: backward ran a second time through the same forward; the saved buffers are released after the first "
+                       "pass (retain_graph is not supported by the HIP engine)")
+
+
+def refuse_updated(net, what, why=None):
+    raise RuntimeError(f"{net}: {what} were updated between this graph's forward and its backward" + (f" ({why})" if why else "")
+                       + ": run backward before the optimizer step")
 
 
 def probe_totals(tag):

@@ -12,6 +12,7 @@ import ctypes as C
 import torch
 
 from . import lib as L
+from . import plans
 from . import slowfast as S
 
 
@@ -404,11 +405,6 @@ def network_backward(ctx, recs, g):
     _stem_bwd(ctx, rf_stem, gfa)
 
 
-def _stamp(params):
-    from .tsf_planes import WEIGHT_EPOCH
-    return tuple(p._version for p in params), WEIGHT_EPOCH[0]
-
-
 class _SlowFastFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, mode, xs_buf, xf_buf, *params):
@@ -422,18 +418,15 @@ class _SlowFastFunction(torch.autograd.Function):
         logits, recs = network_forward(walk, model, xs, xf)
         ctx.walk = walk
         ctx.recs = recs if save else None
-        ctx.stamp = _stamp(params) if save else None
+        ctx.stamp = plans.stamp(params) if save else None
         ctx.params = params
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         if ctx.recs is None:
-            raise RuntimeError("SlowFast: backward ran a second time through the same forward; the saved activations are released after "
-                               "the first pass (retain_graph is not supported by the HIP engine)")
-        if _stamp(ctx.params) != ctx.stamp:
-            raise RuntimeError("SlowFast: parameters were updated between this graph's forward and its backward: run backward before "
-                               "the optimizer step")
+            plans.refuse_second_pass("SlowFast")
+        plans.check_stamp(ctx.params, ctx.stamp, "SlowFast", "the parameters")
         walk = ctx.walk
         need = ctx.needs_input_grad[4:]
         walk.need = {n: bool(r) for n, r in zip(walk.names, need)}

@@ -7,11 +7,14 @@ sequence, not torch autograd over torch ops).
 """
 import ctypes as C
 import os
+import types
 
 import torch
 
 from . import arch
 from . import lib as L
+from . import plans, tsf_planes
+from .tsf_backward import tsf_backward
 
 
 def _as_tokens(x):
@@ -246,22 +249,7 @@ def tsf_forward(model, feat, aux, params, B, F, n, save):
     return logits, s_att, t_att, saved
 
 
-class _StaticAux:
-    """The per-clip side inputs of a recorded forward in static buffers (plans.py): same attributes as _Aux."""
-
-    NAMES = ("mask", "ident", "sizes", "positions")
-
-    def __init__(self, np_, aux):
-        from . import plans
-        for nm in self.NAMES:
-            setattr(self, nm, plans.static_input(np_, "aux_" + nm, getattr(aux, nm)))
-        self.err = aux.err
-
-    def refresh(self, np_, aux):
-        from . import plans
-        for nm in self.NAMES:
-            plans.refresh_input(np_, "aux_" + nm, getattr(aux, nm))
-        self.err = aux.err
+_AUX = ("mask", "ident", "sizes", "positions")       # the per-clip side inputs a recorded forward reads from static buffers
 
 
 class _TSFFunction(torch.autograd.Function):
@@ -273,111 +261,50 @@ class _TSFFunction(torch.autograd.Function):
         # the caller's grad mode comes in through `dims`.  Without it an eval forward would keep every activation and take
         # the training-only split-K + atomics branch.
         save = grad_on and any(ctx.needs_input_grad)
-        from . import tsf_planes, plans
         ctx.model, ctx.dims, ctx.params = model, dims, params
-        ctx.plan = ctx.token = None
         planes = tsf_planes.eligible(model, B * (1 + F * n), save)
-        np_, mode = None, "eager"
+        stream = key = None
         if planes and save and not tsf_planes.dropout_active(model):
             stream = torch.cuda.current_stream(feat.device).cuda_stream
             key = ("tsf", B, F, n, feat.dtype, model.training, model.require_attention, L.deterministic(),
                    tuple(ctx.needs_input_grad[3:]), stream, os.environ.get("MT_PLANES_STREAMK", "0"),
-                   tuple(getattr(aux, nm) is None for nm in _StaticAux.NAMES))
-            np_, mode = plans.lookup(model, key)
-            if mode == "replay" and np_.state_ptrs != plans.state_ptrs(params):
-                plans.drop(model, np_)
-                np_, mode = None, "eager"
-        if mode == "eager":
+                   tuple(getattr(aux, nm) is None for nm in _AUX))
+
+        def body(ins, plan):
+            a = aux if plan is None else types.SimpleNamespace(err=aux.err, **{nm: ins["aux_" + nm] for nm in _AUX})
             if planes:
-                logits, s_att, t_att, saved = tsf_planes.tsf_forward_planes(model, feat, aux, params, B, F, n, save)
+                logits, s_att, t_att, saved = tsf_planes.tsf_forward_planes(model, ins["feat"], a, params, B, F, n, save)
             elif tsf_planes.dropout_active(model):
                 raise NotImplementedError("attn-dropout / ff-dropout > 0 in train mode runs on the plane path only (MT_TSF_PLANES=1, "
                                           "MT_GEMM_SPLIT=1, no MT_TSF_PRUNE_LAST / MT_WGRAD_DEFER, not under stream capture)")
             else:
-                logits, s_att, t_att, saved = tsf_forward(model, feat, aux, params, B, F, n, save)
-            ctx.aux, ctx.saved, ctx.feat = aux, saved, feat
-        elif mode == "record":
-            np_.stream = stream
-            feat_s = plans.static_input(np_, "feat", feat)
-            aux_s = _StaticAux(np_, aux)
-            pl = L.Plan()
-            try:
-                with pl:
-                    logits, s_att, t_att, saved = tsf_planes.tsf_forward_planes(model, feat_s, aux_s, params, B, F, n, True)
-            except Exception:
-                np_.broken = True
-                raise
-            np_.fwd = pl
-            np_.extra.update(saved=saved, outs=(logits, s_att, t_att), aux=aux_s, feat=feat_s)
-            np_.state_ptrs = plans.state_ptrs(params)
-            plans.own(np_, logits)
-            plans.STATS["recorded"] += 1
-        else:
-            plans.refresh_input(np_, "feat", feat)
-            np_.extra["aux"].refresh(np_, aux)
-            np_.extra["saved"]["w_serial"] = tsf_planes.weight_planes_touch(model, params)   # the split launch is in the plan
-            plans.run(np_.fwd)
-            _publish_index_flag(aux.err)
-            logits, s_att, t_att = np_.extra["outs"]
-        if np_ is not None:
-            ctx.plan, ctx.token = np_, np_.begin()
-            ctx.aux, ctx.saved, ctx.feat = np_.extra["aux"], np_.extra["saved"], np_.extra["feat"]
-            # the user-facing outputs are small ([B, classes], two [(B H), 1, N] maps): hand out copies, so that a caller who keeps
-            # predictions on the device across steps does not see the next replay write over them (the eager path returns fresh tensors)
-            logits, s_att, t_att = (None if t is None else t.clone() for t in (logits, s_att, t_att))
-        outs = [logits]
+                logits, s_att, t_att, saved = tsf_forward(model, ins["feat"], a, params, B, F, n, save)
+            if saved is not None:
+                saved.update(feat=ins["feat"], aux=a)        # what the backward reads besides its activations
+            return (logits, s_att, t_att), saved
+        inputs = {"feat": feat, **{"aux_" + nm: getattr(aux, nm) for nm in _AUX}}
+        # a plan's user-facing outputs are small ([B, classes], two [(B H), 1, N] maps): handed out as copies, so that a caller who keeps
+        # predictions on the device across steps does not see the next replay write over them (the eager path returns fresh tensors)
+        logits, s_att, t_att = plans.forward(ctx, model, key, stream, params, inputs, body, clone_outputs=True,
+                                             after_run=lambda np_: _publish_index_flag(aux.err))
         if model.require_attention:
             ctx.mark_non_differentiable(s_att, t_att)
-            outs += [s_att, t_att]
-        return tuple(outs)
+            return logits, s_att, t_att
+        return (logits,)
 
     @staticmethod
     def backward(ctx, dlogits, *unused):
-        from .tsf_backward import tsf_backward
-        from . import plans
-        if ctx.saved is None:
-            raise RuntimeError("SizeInvariantTimeSformer: backward ran a second time through the same forward; the activation "
-                               "buffers are released after the first pass (retain_graph is not supported by the HIP engine)")
-        if ctx.saved.get("planes"):
-            from .tsf_planes import tsf_backward_planes as tsf_backward
-        np_ = ctx.plan
-        dlogits = dlogits.contiguous()
+        s = ctx.saved
         need_df, need_dp = ctx.needs_input_grad[3], ctx.needs_input_grad[4:]
-        if np_ is None:
-            dfeat, dparams = tsf_backward(ctx.model, ctx.feat, ctx.aux, ctx.params, ctx.dims, ctx.saved, dlogits, need_df, need_dp)
-        elif (plans.grads_exist(ctx.params) or torch.cuda.current_stream(dlogits.device).cuda_stream != np_.stream
-              or torch.cuda.is_current_stream_capturing()):
-            plans.STATS["eager_accumulate"] += 1        # see effnet_engine._EffNetFunction.backward
-            dfeat, dparams = tsf_backward(ctx.model, ctx.feat, ctx.aux, ctx.params, ctx.dims, ctx.saved, dlogits, need_df, need_dp,
-                                          keep_saved=True)
-        elif np_.bwd is None:
-            d_s = plans.static_input(np_, "dlogits", dlogits)
-            pl = L.Plan()
-            try:
-                with pl:
-                    dfeat, dparams = tsf_backward(ctx.model, ctx.feat, ctx.aux, ctx.params, ctx.dims, ctx.saved, d_s, need_df,
-                                                  need_dp, keep_saved=True, plan=np_)
-            except Exception:
-                np_.broken = True
-                raise
-            np_.bwd = pl
-            np_.extra.update(grads=list(dparams), dfeat=dfeat)
-            plans.own(np_, dfeat)
-            dparams = plans.fresh_aliases(dparams)
-            dfeat = None if dfeat is None else dfeat.detach()
-        else:
-            from .tsf_planes import check_weight_serial
-            check_weight_serial(ctx.model, ctx.saved)
-            plans.refresh_input(np_, "dlogits", dlogits)
-            plans.run(np_.bwd)
-            L.grads_ready(ctx.model, ctx.params, np_.extra["flat_grads"])
-            dfeat = None if np_.extra["dfeat"] is None else np_.extra["dfeat"].detach()
-            dparams = plans.fresh_aliases(np_.extra["grads"])
-        ctx.saved = None
-        if np_ is not None:
-            np_.release(ctx.token)
-            ctx.token = None
-        return (None, None, None, dfeat) + tuple(dparams)
+
+        def body(g, keep_saved, plan):
+            if s.get("planes"):
+                dfeat, dparams = tsf_planes.tsf_backward_planes(ctx.model, s["feat"], s["aux"], ctx.params, ctx.dims, s, g, need_df,
+                                                                need_dp, keep_saved=keep_saved, plan=plan)
+            else:
+                dfeat, dparams = tsf_backward(ctx.model, s["feat"], s["aux"], ctx.params, ctx.dims, s, g, need_df, need_dp)
+            return (dfeat,), dparams
+        return (None, None, None) + plans.backward(ctx, "SizeInvariantTimeSformer", dlogits.contiguous(), body)
 
 
 _CHAIN_STREAMS = {}
@@ -416,7 +343,6 @@ def tsf_apply(model, x, mask, identities_mask, size_embedding, positions):
         # sequences on their own streams.  One sequence leaves the matrix cores idle during its LayerNorm / attention / epilogue
         # phases and the tile tails; a second one fills them (measured in-step: two co-running kernels each stretch ~1.4x, not 2x).
         main = torch.cuda.current_stream(x.device)
-        from . import tsf_planes
         presplit = tsf_planes.eligible(model, (b // chains) * (1 + f * h * w), grad_on)
         if presplit:
             # the chains share the weights' operand planes: write them ONCE on the main stream, before the fork (each chain re-writing

@@ -21,9 +21,7 @@ import torch
 
 from . import arch
 from . import lib as L
-
-# bumped by the fused optimizers (optim.py): they update parameters through raw pointers, which torch's version counters do not see
-WEIGHT_EPOCH = [0]
+from . import plans
 
 # LayerNorm backward: parameter-gradient column sums folded into the rows kernel as per-block partials (MT_LN_FOLD=0: the second pass
 # over dy / x / dx on the weight-gradient stream)
@@ -76,40 +74,15 @@ def weight_planes(model, params, training):
             first += t.shape[1] * t.shape[2]
         host = torch.tensor(rows, dtype=torch.int64).pin_memory()
         cache = dict(ident=ident, holder=holder, host=host, table=host.to(dev, non_blocking=True), blocks=first, count=len(rows),
-                     stamp=None)
+                     serial=plans.PlaneSerial("the Linear weights"))
         model._wplanes_cache = cache
     # The planes are re-written on EVERY forward (one launch, ~60 us for the 54 matrices): updates that move no version counter
     # (p.data.copy_, dist.broadcast(p.data), a fused optimizer step through raw pointers) cannot leave them stale, and a forward
     # captured into a HIP graph (harness.GraphedEval) holds the split as a node, so its replays read the weights of the replay's time.
-    stamp = (tuple(w._version for w in ws), WEIGHT_EPOCH[0])
-    if model.__dict__.get("_wplanes_presplit"):      # MT_TSF_CHAINS: tsf_apply split once, before the chains' streams forked
-        return cache["holder"], cache["serial"]
-    L.check(lib.mt_split_planes_blk_multi(L.ptr(cache["table"]), cache["count"], cache["blocks"], L.stream_ptr()),
-            "mt_split_planes_blk_multi")             # (L.ptr: a launch plan being recorded pins the table)
-    if cache["stamp"] != stamp:                      # the weights changed since the planes were last written: graphs that saved the
-        cache["serial"] = cache.get("serial", 0) + 1          # old serial must not run their backward on the new planes
-    cache["stamp"] = stamp
-    return cache["holder"], cache["serial"]
-
-
-def weight_planes_touch(model, params):
-    """Bookkeeping of weight_planes() for a replayed forward (the split launch itself is part of the recorded phase): a new serial
-    when the weights changed since the planes were last written.  Returns the serial the replayed forward's planes carry."""
-    cache = model._wplanes_cache
-    wts = list(params[5:5 + 16 * model.depth])
-    ws = [wts[16 * li + off] for li in range(model.depth) for off in _SEL]
-    stamp = (tuple(w._version for w in ws), WEIGHT_EPOCH[0])
-    if cache["stamp"] != stamp:
-        cache["serial"] = cache.get("serial", 0) + 1
-        cache["stamp"] = stamp
-    return cache["serial"]
-
-
-def check_weight_serial(model, saved):
-    cache = getattr(model, "_wplanes_cache", None)
-    if cache is None or cache.get("serial") != saved["w_serial"]:
-        raise RuntimeError("SizeInvariantTimeSformer: the Linear weights were updated between this graph's forward and its backward "
-                           "(their operand planes were rewritten by a later forward): run backward before the optimizer step")
+    if not model.__dict__.get("_wplanes_presplit"):  # MT_TSF_CHAINS: tsf_apply split once, before the chains' streams forked
+        L.check(lib.mt_split_planes_blk_multi(L.ptr(cache["table"]), cache["count"], cache["blocks"], L.stream_ptr()),
+                "mt_split_planes_blk_multi")         # (L.ptr: a launch plan being recorded pins the table)
+    return cache["holder"], cache["serial"].touch(ws)
 
 
 def _new(dev, *shape):
@@ -139,7 +112,7 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
             "mt_embed_fwd")
     _publish_index_flag(aux.err)
 
-    saved = {"layers": [], "planes": True, "w_serial": serial} if save else None
+    saved = {"layers": [], "planes": True, "wp": wp, "w_serial": serial} if save else None
     drop = dropout_active(model)
     p_att, p_ff = (float(model.attn_dropout), float(model.ff_dropout)) if drop else (0.0, 0.0)
     want_att = model.require_attention
@@ -232,8 +205,7 @@ def tsf_backward_planes(model, feat, aux, params, dims, saved, dlogits, need_dfe
     M = B * N
     eps = arch.LN_EPS
     scale = float(dh) ** -0.5
-    check_weight_serial(model, saved)
-    wp = model._wplanes_cache["holder"]
+    wp = saved["wp"]
     grads, flat_grads = L.zero_grads(list(params), with_flat=True)
     P = list(params)
     idx = len(P)

@@ -8,6 +8,7 @@ import torch
 
 from . import arch
 from . import lib as L
+from . import plans
 from .effnet_engine import SLOTS, _StatsPool, _BNCtx, _track, _bump_tracked
 
 RELU, NONE = 2, 0
@@ -92,8 +93,7 @@ class _WeightPlanes:
         self.items = {}          # weight data_ptr -> (weight, planes, co, ci)
         self.table = None
         self.fresh = False
-        self.serial, self.stamp = 0, None     # see tsf_planes.weight_planes: graphs that saved an older serial must not run their
-                                              # backward on planes a later forward re-split from updated weights
+        self.serial = plans.PlaneSerial("the pointwise weights")
 
     def begin(self, lib):
         self.fresh = False
@@ -114,16 +114,6 @@ class _WeightPlanes:
         self.items[w_pw.data_ptr()] = (w_pw, planes, co, ci)
         self.table = None
         return planes
-
-    def touch(self):
-        """A new serial when the weights changed since the planes were last written (version counters; the fused optimizers that
-        write through raw pointers bump tsf_planes.WEIGHT_EPOCH)."""
-        from .tsf_planes import WEIGHT_EPOCH
-        stamp = (tuple(w._version for w, _, _, _ in self.items.values()), tuple(self.items), WEIGHT_EPOCH[0])
-        if stamp != self.stamp:
-            self.serial += 1
-            self.stamp = stamp
-        return self.serial
 
     def end(self, dev):
         if self.table is not None or not self.items:
@@ -280,8 +270,9 @@ def xception_forward(model, x, params, training, save, plan=None):
         saved["tail"] = tail
     if planes_on:
         wplanes.end(dev)
+        w_serial = wplanes.serial.touch([w for w, _, _, _ in wplanes.items.values()])
         if save:
-            saved["w_serial"] = wplanes.touch()
+            saved["w_serial"] = w_serial
     _bump_tracked(plan)
     return feat, saved, cur.H
 
@@ -290,9 +281,6 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
     """keep_saved: the activation records belong to a launch plan (plans.py) and stay for its next replay; plan: the NetPlan whose
     backward phase is being recorded (it keeps the flat gradient buffer)."""
     lib = L.get()
-    if "w_serial" in saved and model.__dict__["_xc_wplanes"].serial != saved["w_serial"]:
-        raise RuntimeError("Xception: the pointwise weights were updated between this graph's forward and its backward (their operand "
-                           "planes were rewritten by a later forward): run backward before the optimizer step")
     dev = dfeat.device
     N, H, W = shape
     P = list(params)
@@ -513,97 +501,33 @@ class _XceptionFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, x_nhwc, *params):
-        from . import plans
         model, grad_on = model
         save = grad_on and any(ctx.needs_input_grad)      # see tsf_engine._TSFFunction.forward
         N, H, W, _ = x_nhwc.shape
         ctx.shape = (N, H, W)
         ctx.model, ctx.params, ctx.training = model, params, model.training
-        ctx.plan = ctx.token = None
-        np_, mode = None, "eager"
+        stream = key = state = None
         if save and _plannable() and W <= 512 and L.gemm_split_enabled():
             stream = torch.cuda.current_stream(x_nhwc.device).cuda_stream
+            state = list(params) + list(model.buffers())       # (what a recording holds the addresses of)
             key = ("xc", tuple(x_nhwc.shape), x_nhwc.dtype, model.training, L.deterministic(), tuple(ctx.needs_input_grad[2:]), stream,
                    float(model.bn1.momentum), float(model.bn1.eps))
-            np_, mode = plans.lookup(model, key)
-            if mode == "replay" and np_.state_ptrs != plans.state_ptrs(list(params) + list(model.buffers())):
-                plans.drop(model, np_)                   # parameters / buffers moved: record afresh later
-                np_, mode = None, "eager"
-        if mode == "eager":
-            feat, saved, ho = xception_forward(model, x_nhwc, params, model.training, save)
-            ctx.saved = saved
-            return feat
-        if mode == "record":
-            np_.stream = stream
-            x_s = plans.static_input(np_, "x", x_nhwc)
-            pl = L.Plan()
-            try:
-                with pl:
-                    feat, saved, _ = xception_forward(model, x_s, params, model.training, True, plan=np_)
-            except Exception:
-                np_.broken = True
-                raise
-            np_.fwd = pl
-            np_.extra.update(saved=saved, feat=feat)
-            np_.state_ptrs = plans.state_ptrs(list(params) + list(model.buffers()))
-            plans.own(np_, feat)
-            plans.STATS["recorded"] += 1
-        else:
-            plans.refresh_input(np_, "x", x_nhwc)
-            plans.run(np_.fwd)
-            if "w_serial" in np_.extra["saved"]:
-                np_.extra["saved"]["w_serial"] = model.__dict__["_xc_wplanes"].touch()      # the split launch is in the plan
-            if np_.extra.get("tracked"):
-                torch._foreach_add_(np_.extra["tracked"], 1)
-        ctx.plan, ctx.token = np_, np_.begin()
-        ctx.saved = np_.extra["saved"]
-        return np_.extra["feat"].detach()
+
+        def body(ins, plan):
+            feat, saved, _ = xception_forward(model, ins["x"], params, model.training, save, plan=plan)
+            return (feat,), saved
+        feat, = plans.forward(ctx, model, key, stream, state, {"x": x_nhwc}, body)
+        return feat
 
     @staticmethod
     def backward(ctx, dfeat):
-        if ctx.saved is None:
-            raise RuntimeError("Xception: backward ran a second time through the same forward; the activation buffers are "
-                               "released after the first pass (retain_graph is not supported by the HIP engine)")
         if ctx.needs_input_grad[1]:
             raise NotImplementedError("gradient w.r.t. the input crops is not part of the MINTIME training path")
-        from . import plans
-        np_ = ctx.plan
-        if "w_serial" in ctx.saved and ctx.model.__dict__["_xc_wplanes"].serial != ctx.saved["w_serial"]:
-            raise RuntimeError("Xception: the pointwise weights were updated between this graph's forward and its backward (their operand "
-                               "planes were rewritten by a later forward): run backward before the optimizer step")
-        dfeat = dfeat.contiguous()
-        need = ctx.needs_input_grad[2:]
-        if np_ is None:
-            dparams = xception_backward(ctx.model, ctx.params, ctx.saved, ctx.shape, ctx.training, dfeat, need)
-        elif (plans.grads_exist(ctx.params) or torch.cuda.current_stream(dfeat.device).cuda_stream != np_.stream
-              or torch.cuda.is_current_stream_capturing()):
-            # existing gradients are ADDED to by autograd (they alias the plan's gradient buffer): eager sequence over the plan's
-            # saved activations, which stay for the next replay
-            plans.STATS["eager_accumulate"] += 1
-            dparams = xception_backward(ctx.model, ctx.params, ctx.saved, ctx.shape, ctx.training, dfeat, need, keep_saved=True)
-        elif np_.bwd is None:
-            d_s = plans.static_input(np_, "dfeat", dfeat)
-            pl = L.Plan()
-            try:
-                with pl:
-                    dparams = xception_backward(ctx.model, ctx.params, ctx.saved, ctx.shape, ctx.training, d_s, need, keep_saved=True,
-                                                plan=np_)
-            except Exception:
-                np_.broken = True
-                raise
-            np_.bwd = pl
-            np_.extra.update(grads=list(dparams))
-            dparams = plans.fresh_aliases(dparams)
-        else:
-            plans.refresh_input(np_, "dfeat", dfeat)
-            plans.run(np_.bwd)
-            L.grads_ready(ctx.model, list(ctx.params), np_.extra["flat_grads"])
-            dparams = plans.fresh_aliases(np_.extra["grads"])
-        ctx.saved = None
-        if np_ is not None:
-            np_.release(ctx.token)
-            ctx.token = None
-        return (None, None) + tuple(dparams)
+
+        def body(g, keep_saved, plan):
+            return (), xception_backward(ctx.model, ctx.params, ctx.saved, ctx.shape, ctx.training, g, ctx.needs_input_grad[2:],
+                                         keep_saved=keep_saved, plan=plan)
+        return (None, None) + plans.backward(ctx, "Xception", dfeat.contiguous(), body)
 
 
 def xception_apply(model, inputs):

@@ -524,3 +524,36 @@ def test_project_operand_planes_and_the_gemm_on_them(n_img, hw, C, Co):
     ref = torch.empty(rows, Co, device="cuda")
     L.gemm(L.OP_NT, z, w, ref, rows, Co, C, C, C, Co, prologue=L.PRO_BN_SWISH_GATE, scale=sc, shift=sh, gate=gate, hw=hw)
     assert_close(out, ref, 2e-5, "plane operands vs the operand-prologue GEMM")
+
+
+def test_a_forward_at_another_batch_size_leaves_a_pending_backward_alone():
+    """The weight planes belong to the plane selection of a batch size (effnet_engine.weight_planes): a no_grad forward at 8 crops,
+    between a training forward at 16 crops and its backward, selects other convolutions and writes other planes -- the backward runs,
+    and its gradients are bit for bit those of the same sequence without the 8-crop forward (deterministic mode)."""
+    from mintime_amd import effnet_engine, lib as L
+    m, _ = _model(5, True)
+    scope16, scope8 = effnet_engine.planes_scope(m, 16), effnet_engine.planes_scope(m, 8)
+    if not any(scope8[0] + scope8[1] + [scope8[2]]):
+        pytest.skip("the plane path is off (MT_EF_PLANES=0 / MT_GEMM_SPLIT=0)")
+    assert scope16 != scope8
+    x16, x8 = _input(16, 5).cuda(), _input(8, 6).cuda()
+    dfeat = torch.randn(16, 1280, 7, 7, generator=torch.Generator().manual_seed(7)).cuda()
+
+    def grads(with_small_forward):
+        model, _ = _model(5, True)
+        feats = model(x16)
+        if with_small_forward:
+            with torch.no_grad():
+                model(x8)
+        feats.backward(dfeat)
+        torch.cuda.synchronize()
+        return {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
+
+    prev = L.set_deterministic(True)
+    try:
+        want, got = grads(False), grads(True)
+    finally:
+        L.set_deterministic(prev)
+    assert len(want) > 200 and got.keys() == want.keys()
+    diff = [n for n in want if not torch.equal(got[n], want[n])]
+    assert not diff, f"{len(diff)} of {len(want)} gradients differ, e.g. {diff[:5]}"

@@ -333,3 +333,26 @@ def test_dataparallel_is_transparent():
     m2.blocks[6].proj = torch.nn.Linear(2304, 1)
     m2.load_state_dict(sd)
 
+
+
+def test_second_backward_and_replaced_or_updated_parameters_are_refused():
+    """The saved walk was formed from the forward's parameters: a second backward, a parameter updated in place and a parameter whose
+    storage was replaced after the forward are refused (plans.check_stamp)."""
+    m, _ = _model(seed=2, head=SMALL_HEAD)
+    m.train()
+    slow, fast = _small_inputs(2, 3)
+    x = [slow.to(dev), fast.to(dev)]
+    y = m(x)
+    y.sum().backward(retain_graph=True)
+    with pytest.raises(RuntimeError, match="second time"):
+        y.sum().backward()
+    w = m.blocks[6].proj.weight
+    y = m(x)
+    with torch.no_grad():
+        w.mul_(2.0)
+    with pytest.raises(RuntimeError, match="updated between"):
+        y.sum().backward()
+    y = m(x)
+    w.data = w.data.clone()                          # same values, new storage: the version counter does not move
+    with pytest.raises(RuntimeError, match="updated between"):
+        y.sum().backward()

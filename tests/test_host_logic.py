@@ -106,6 +106,58 @@ def test_launch_plan_registry_state_machine(monkeypatch):
     assert plans.lookup(m, "a") == (None, "eager")
 
 
+def test_weight_stamp_and_plane_serial_refuse_only_changed_weights(monkeypatch):
+    """plans.stamp / check_stamp (values derived per forward) and plans.PlaneSerial (persistent weight planes): an in-place update,
+    a new storage or a fused-optimizer epoch bump refuses a pending backward; re-splitting the same weights, into this holder or into
+    another one (another batch size's selection), or growing the holder does not."""
+    from mintime_amd import plans
+    monkeypatch.setattr(plans, "WEIGHT_EPOCH", [0])
+    ws = [torch.randn(4, 3), torch.randn(5)]
+
+    def refused(saved_by_forward, touch_between=None):
+        if touch_between is not None:
+            touch_between()
+        try:
+            plans.check_planes({"w_serial": saved_by_forward}, "Net")
+            return False
+        except RuntimeError as e:
+            assert "Net: the w were updated between" in str(e)
+            return True
+
+    def derived_refused(taken):
+        try:
+            plans.check_stamp(ws, taken, "Net", "the w")
+            return False
+        except RuntimeError as e:
+            assert "updated between" in str(e)
+            return True
+
+    ser, other = plans.PlaneSerial("the w"), plans.PlaneSerial("the w")
+    taken = plans.stamp(ws)
+    saved = ser.touch(ws)
+    assert not derived_refused(taken)
+    assert not refused(saved, lambda: ser.touch(ws))                    # re-split from the same weights
+    assert not refused(saved, lambda: ser.touch())                      # (a replayed forward: the same tensors)
+    assert not refused(saved, lambda: other.touch(ws))                  # another holder of the same weights
+    assert not refused(saved, lambda: ser.touch(ws + [torch.randn(2)]))  # the holder grew
+    saved = ser.touch(ws)                                               # (and shrank back: a new serial)
+    assert not refused(saved)
+
+    ws[0].add_(1.0)                                                     # in-place update: the version counter moves
+    assert derived_refused(taken)
+    assert not refused(saved)                                           # ... the planes are only stale once a forward re-splits them
+    assert refused(saved, lambda: ser.touch(ws))
+
+    taken, saved = plans.stamp(ws), ser.touch(ws)
+    ws[1] = ws[1].clone()                                               # new storage
+    assert derived_refused(taken) and refused(saved, lambda: ser.touch(ws))
+
+    taken, saved = plans.stamp(ws), ser.touch(ws)
+    plans.WEIGHT_EPOCH[0] += 1                                          # a fused optimizer wrote through raw pointers
+    assert derived_refused(taken) and refused(saved, lambda: ser.touch())
+    assert not refused(other.touch(ws), lambda: other.touch(ws))
+
+
 def test_errors_are_reported_not_swallowed():
     h = lib.get()
     d = lib.GemmDesc()          # all-null descriptor
