@@ -14,7 +14,7 @@
  *     never allocates; scratch comes from the caller
  *   - return 0 on success, negative on error; mt_last_error() gives a thread-local message
  *   - re-entrant: launches go to the caller's stream on the current device; the only process-wide state are two switches
- *     (mt_gemm_set_split, mt_set_deterministic) and, with the latter on, the per-stream workspace described there
+ *     (mt_gemm_set_split, mt_set_deterministic; since 122 also the arithmetic tier, mt_gemm_set_precision) and, with the latter on, the per-stream workspace described there
  */
 #ifndef MINTIME_HIP_H
 #define MINTIME_HIP_H
@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MT_VERSION 121
+#define MT_VERSION 122
 
 int mt_version(void);
 const char* mt_last_error(void);
@@ -116,6 +116,25 @@ int mt_gemm(const mt_gemm_desc* d, void* stream);
  * Process-wide; returns the previous setting.  Inputs, outputs and accumulators are fp32 either way. */
 int mt_gemm_set_split(int on);
 int mt_gemm_get_split(void);
+
+/* Arithmetic tier of the bf16-pipe contractions: everything on mt_gemm_planes and the split-operand loop of mt_gemm.
+ *   MT_PRECISION_HIGHEST (default): the six leading piece products of the three-piece split, fp32-level error.
+ *   MT_PRECISION_HIGH: the three products a0 b0 + a0 b1 + a1 b0 of the first two pieces of the SAME split (the "bf16x3" of
+ *     torch.set_float32_matmul_precision("high"); gfx950 has no TF32).  About 16 mantissa bits per operand:
+ *     |error| <= 3.1 * 2^-16 * sum|a||b| plus the fp32 accumulation error.  Half the matrix instructions; the plane loop reads two of
+ *     an operand's three planes (producers still write all three: one plane tensor serves both tiers).
+ * Accumulators, layouts, epilogues, the balanced accumulators and deterministic mode are the same at both tiers.  With
+ * mt_gemm_set_split(0) the tier has no effect on mt_gemm: the fp32 pipe is exact (mt_gemm_planes has no fp32-pipe form and follows
+ * the tier).  Not covered (fp32 MFMA at either tier): the attention cores, contractions with K < 512 or an operand prologue the split
+ * loop does not take, the depthwise / squeeze-excite / stem kernels and the 3-D convolutions.
+ * Process-wide and read when a call is DISPATCHED: a recorded launch plan replays at the tier current at replay.
+ * mt_gemm_set_precision returns the previous level; an unknown level returns MT_ERR_ARG = -1 (mt_last_error() says why) and changes
+ * nothing.  MT_MATMUL_PRECISION=highest|high in the environment sets the initial level; any other value keeps highest and is
+ * reported through mt_last_error() by the first mt_gemm_get_precision(). */
+#define MT_PRECISION_HIGHEST 0
+#define MT_PRECISION_HIGH 1
+int mt_gemm_set_precision(int level);
+int mt_gemm_get_precision(void);
 
 /* planes[p][i], p = 0..2: the exact three-piece bf16 split of src[i] (x = x0 + x1 + x2, round-to-nearest at each level) that the
  * split-operand loop computes on the fly -- done once for operands that many launches share (weights: once per optimizer step).

@@ -11,6 +11,7 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 from . import arch, synth, lib  # noqa: F401,E402
+from .lib import set_matmul_precision, get_matmul_precision, matmul_precision  # noqa: F401,E402
 from . import timesformer, tsf_engine, tsf_backward  # noqa: F401
 from . import efficientnet, effnet_engine, effnet_backward  # noqa: F401
 from . import ddp, optim, harness, sequence, plans  # noqa: F401
@@ -24,4 +25,4 @@ from . import slowfast, slowfast_engine  # noqa: F401,E402
 from .slowfast import SlowFast, slowfast_r50, slowfast_input_transform  # noqa: F401,E402
 
 __all__ = ["arch", "synth", "lib", "timesformer", "tsf_engine", "SizeInvariantTimeSformer", "efficientnet", "effnet_engine", "EfficientNet",
-           "baseline", "Baseline", "slowfast", "SlowFast", "slowfast_r50", "slowfast_input_transform"]
+           "baseline", "Baseline", "slowfast", "SlowFast", "slowfast_r50", "slowfast_input_transform", "set_matmul_precision", "get_matmul_precision", "matmul_precision"]

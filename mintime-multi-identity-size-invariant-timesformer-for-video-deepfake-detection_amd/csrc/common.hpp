@@ -56,6 +56,9 @@ int stem_wgrad_mfma(const float* du, const float* z, const float* kabc, const vo
 
 enum { MT_ERR_ARG = -1, MT_ERR_LAUNCH = -2, MT_ERR_UNSUPPORTED = -3 };
 
+// gemm_split.hip: the current arithmetic tier of the bf16-pipe contractions (MT_PRECISION_HIGHEST / MT_PRECISION_HIGH)
+int matmul_precision();
+
 // BatchNorm partial sums [slots][2][C] (fp64 accumulators fed by one atomic per block and channel).  Default: fp64 atomics -- the
 // order in which blocks arrive shows in the last bits.  Deterministic mode (the ABI's `slots` argument NEGATIVE: |slots| accumulators):
 // every accumulator is two 64-bit INTEGER limbs, `limb` = |slots| * 2 * C doubles apart, and a block's fp32 partial v is added as

@@ -3,7 +3,7 @@
 // step, the head's gradient of the residual stream).
 #include "../../include/mintime_hip.h"
 #include "common.hpp"
-#include "gemm_planes.hpp"
+#include "gemm_planes_launch.hpp"
 #include "det.hpp"
 #include <stdlib.h>
 #include <string.h>
@@ -103,19 +103,6 @@ int persist_blocks() {
   return g_persist;
 }
 
-template <bool AKM, bool BKM, int EPI, int BAL, bool CPL, int SK = 0>
-int launch_planes(const GemmArgs& a, dim3 grid, hipStream_t s) {
-  constexpr int ST = 2;
-  auto k = gemm_planes_kernel<2, 2, 2, 2, AKM, BKM, EPI, ST, BAL == BAL_PAIR ? 2 : 3, BAL, CPL, SK>;
-  constexpr size_t lds = (size_t)ST * 3 * (128 + 128) * 32;
-  {
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds);
-    if (e != hipSuccess) return fail(MT_ERR_LAUNCH, "mt_gemm_planes: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-  }
-  hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);
-  return check_launch("mt_gemm_planes");
-}
-
 }  // namespace
 
 extern "C" int mt_gemm_planes_set_persist(int blocks_per_cu) {
@@ -173,6 +160,12 @@ static int gemm_planes_impl(const mt_gemm_planes_desc* d, void* stream) {
   if (epi == MT_EPI_GEGLU_BWD && (!d->C2 || d->n_half != d->N || (d->n_half & 31)))
     return fail(MT_ERR_ARG, "mt_gemm_planes GEGLU_BWD: needs C2, n_half == N and n_half %% 32 == 0");
   hipStream_t s = (hipStream_t)stream;
+  // arithmetic tier, read at dispatch (a recorded plan replays through here): pieces read per operand
+  const bool high = matmul_precision() == MT_PRECISION_HIGH;
+  const int np = high ? 2 : 3;
+  auto launch = [&](int skm, const GemmArgs& ga, dim3 g) {
+    return high ? launch_planes_high(op, epi, cpl, skm, ga, g, s) : launch_planes_form<3>(op, epi, cpl, skm, ga, g, s);
+  };
 
   // operand geometry as stored: A is [M][K] (NT, NN) or [K][M] (TN); B is [N][K] (NT) or [K][N] (NN, TN)
   const int a_rows = op == MT_OP_TN ? d->K : d->M, a_cols = op == MT_OP_TN ? d->M : d->K;
@@ -215,7 +208,7 @@ static int gemm_planes_impl(const mt_gemm_planes_desc* d, void* stream) {
     a.k_chunk = chunk; a.xcd_k = 1;
     grid.y = (unsigned)(((d->K + chunk - 1) / chunk + 7) / 8 * 8);
     if (int rc = det_gemm_setup(a.C, a.ldc, a.det_slab, d->M, d->N, (d->K + chunk - 1) / chunk, false, s)) return rc;
-    return launch_planes<true, true, EPI_ATOMIC, BAL_NONE, false, 0>(a, grid, s);
+    return launch(0, a, grid);
   }
   {
     // forward / data-gradient GEMMs sit on the critical queue, the weight gradients they share the matrix cores with do not
@@ -223,7 +216,7 @@ static int gemm_planes_impl(const mt_gemm_planes_desc* d, void* stream) {
     a.wave_prio = prio;
   }
   if (m_tiles >= 32 && n_tiles >= 2 && !getenv("MT_NO_L2_BLOCKING")) {
-    const int64_t panel = (int64_t)128 * d->K * 6;   // one column group's B panels: three bf16 planes
+    const int64_t panel = (int64_t)128 * d->K * 2 * np;   // one column group's B panels: the bf16 planes the loop reads
     static const int64_t group_bytes = getenv("MT_PLANES_GROUP_KB") ? (int64_t)atoi(getenv("MT_PLANES_GROUP_KB")) << 10 : (2 << 20);
     int gn = (int)(group_bytes / (panel > 0 ? panel : 1));
     if (gn < 1) gn = 1;
@@ -256,26 +249,13 @@ static int gemm_planes_impl(const mt_gemm_planes_desc* d, void* stream) {
     const int g = cu_count() * per_cu / 8 * 8;
     if (per_cu > 0 && g >= 8 && m_tiles * n_tiles > g) {
       const dim3 pg((unsigned)g, 1, 1);
-      if (op == MT_OP_NT && epi == MT_EPI_STORE) return launch_planes<false, false, EPI_STORE, BAL_PAIR, false, 2>(a, pg, s);
-      if (op == MT_OP_NT && epi == MT_EPI_BIAS_RES) return launch_planes<false, false, EPI_BIAS_RES, BAL_PAIR, false, 2>(a, pg, s);
-      if (op == MT_OP_NN && epi == MT_EPI_STORE) return launch_planes<false, true, EPI_STORE, BAL_PAIR, false, 2>(a, pg, s);
+      // the forms that have a persistent instance (gemm_planes_launch.hpp); NN BIAS_RES goes on to one block per tile
+      const bool nt_store = op == MT_OP_NT && epi == MT_EPI_STORE, nt_bias_res = op == MT_OP_NT && epi == MT_EPI_BIAS_RES;
+      const bool nn_store = op == MT_OP_NN && epi == MT_EPI_STORE;
+      if (nt_store || nt_bias_res || nn_store) return launch(2, a, pg);
     }
   }
-#define PL_COMBO(OP, BKM_, EPI_, CPL_) \
-  if (op == OP && epi == EPI_ && cpl == CPL_)                                                       \
-    return sk ? launch_planes<false, BKM_, EPI_, BAL_PAIR, CPL_, 1>(a, grid, s)                     \
-              : launch_planes<false, BKM_, EPI_, BAL_PAIR, CPL_, 0>(a, grid, s);
-  PL_COMBO(MT_OP_NT, false, EPI_STORE, false)
-  PL_COMBO(MT_OP_NT, false, EPI_BIAS_RES, false)
-  PL_COMBO(MT_OP_NT, false, EPI_STATS, false)
-  PL_COMBO(MT_OP_NT, false, EPI_GEGLU, false)
-  PL_COMBO(MT_OP_NT, false, EPI_GEGLU, true)
-  PL_COMBO(MT_OP_NN, true, EPI_STORE, false)
-  PL_COMBO(MT_OP_NN, true, EPI_BIAS_RES, false)
-  PL_COMBO(MT_OP_NN, true, EPI_GEGLU_BWD, false)
-  PL_COMBO(MT_OP_NN, true, EPI_GEGLU_BWD, true)
-#undef PL_COMBO
-  return fail(MT_ERR_UNSUPPORTED, "mt_gemm_planes: unsupported op / epilogue %d / %d", op, epi);
+  return launch(sk ? 1 : 0, a, grid);
 }
 
 extern "C" int mt_gemm_planes(const mt_gemm_planes_desc* d, void* stream) {

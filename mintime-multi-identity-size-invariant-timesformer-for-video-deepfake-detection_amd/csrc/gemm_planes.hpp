@@ -229,7 +229,9 @@ __device__ __forceinline__ void sk_tile_coords(const GemmArgs& p, int t, int& mt
 // zeros).
 // SKM: 0 = one block per tile, 1 = stream-K (below), 2 = persistent blocks that walk their XCD's share of the tile list and issue
 // the NEXT tile's first stage before the current tile's epilogue (the per-tile pipeline fill that K = 512 problems pay on every tile)
-template <int WAVES_M, int WAVES_N, int TM, int TN, bool AKM, bool BKM, int EPI, int STAGES, int MINW, int BAL, bool CPL = false, int SKM = 0>
+// NP: pieces read per operand.  3 = the six products above (MT_PRECISION_HIGHEST).  2 = MT_PRECISION_HIGH: a0 b0 + a0 b1 + a1 b0 -- a stage
+// holds planes 0 and 1 only (the third plane of the plane-major tensor is never fetched), three MFMA groups per k-step.
+template <int WAVES_M, int WAVES_N, int TM, int TN, bool AKM, bool BKM, int EPI, int STAGES, int MINW, int BAL, bool CPL = false, int SKM = 0, int NP = 3>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW)
 void gemm_planes_kernel(const GemmArgs p) {
   constexpr int NW = WAVES_M * WAVES_N;
@@ -237,9 +239,10 @@ void gemm_planes_kernel(const GemmArgs p) {
   constexpr int BN = WAVES_N * TN * 32;
   constexpr int BK = 16;
   constexpr int A_PLANE = BM * 32, B_PLANE = BN * 32;            // bytes per plane per stage
-  constexpr int STAGE = 3 * (A_PLANE + B_PLANE);
+  static_assert(NP == 2 || NP == 3, "two or three pieces per operand");
+  constexpr int STAGE = NP * (A_PLANE + B_PLANE);
   constexpr int PPA = A_PLANE / 1024, PPB = B_PLANE / 1024;       // 1 KB pieces per plane
-  constexpr int PA = 3 * PPA, PB = 3 * PPB;
+  constexpr int PA = NP * PPA, PB = NP * PPB;
   static_assert((PA + PB) % NW == 0, "every wavefront must issue the same number of DMA pieces");
   constexpr int IPW = (PA + PB) / NW;
   static_assert(STAGES >= 2 && STAGES <= 4, "2..4 stages");
@@ -290,7 +293,7 @@ void gemm_planes_kernel(const GemmArgs p) {
     }
   }
 
-  struct Frags { bf16x8_t a0[TM], a1[TM], a2[TM], b0[TN], b1[TN], b2[TN]; };
+  struct Frags { bf16x8_t a0[TM], a1[TM], a2[NP == 3 ? TM : 1], b0[TN], b1[TN], b2[NP == 3 ? TN : 1]; };
   typedef __attribute__((address_space(3))) s16x4_t* lds_tr_p;
   typedef __attribute__((address_space(3))) const unsigned char* lds_cp;
   auto tr_read = [&](const unsigned char* base) -> bf16x8_t {
@@ -304,14 +307,14 @@ void gemm_planes_kernel(const GemmArgs p) {
 
   auto read_frags = [&](int slot, Frags& f) {
     const unsigned char* sa = smem_pl + slot * STAGE;
-    const unsigned char* sb = sa + 3 * A_PLANE;
+    const unsigned char* sb = sa + NP * A_PLANE;
     if (MT_PLANES_ABLATE & 4) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) { f.a0[i][e] = (__bf16)(float)(lane + e + i); f.a1[i][e] = (__bf16)(float)(lane - e); f.a2[i][e] = (__bf16)(float)(lane ^ e); }
+        for (int i = 0; i < TM; ++i) { f.a0[i][e] = (__bf16)(float)(lane + e + i); f.a1[i][e] = (__bf16)(float)(lane - e); if constexpr (NP == 3) f.a2[i][e] = (__bf16)(float)(lane ^ e); }
 #pragma unroll
-        for (int j = 0; j < TN; ++j) { f.b0[j][e] = (__bf16)(float)(lane * 2 + e + j); f.b1[j][e] = (__bf16)(float)(lane + 3 * e); f.b2[j][e] = (__bf16)(float)(3 + e); }
+        for (int j = 0; j < TN; ++j) { f.b0[j][e] = (__bf16)(float)(lane * 2 + e + j); f.b1[j][e] = (__bf16)(float)(lane + 3 * e); if constexpr (NP == 3) f.b2[j][e] = (__bf16)(float)(3 + e); }
       }
       return;
     }
@@ -320,11 +323,11 @@ void gemm_planes_kernel(const GemmArgs p) {
       if constexpr (!AKM) {
         f.a0[i] = *reinterpret_cast<const bf16x8_t*>(sa + a_frag[i]);
         f.a1[i] = *reinterpret_cast<const bf16x8_t*>(sa + A_PLANE + a_frag[i]);
-        f.a2[i] = *reinterpret_cast<const bf16x8_t*>(sa + 2 * A_PLANE + a_frag[i]);
+        if constexpr (NP == 3) f.a2[i] = *reinterpret_cast<const bf16x8_t*>(sa + 2 * A_PLANE + a_frag[i]);
       } else {
         f.a0[i] = tr_read(sa + a_frag[i]);
         f.a1[i] = tr_read(sa + A_PLANE + a_frag[i]);
-        f.a2[i] = tr_read(sa + 2 * A_PLANE + a_frag[i]);
+        if constexpr (NP == 3) f.a2[i] = tr_read(sa + 2 * A_PLANE + a_frag[i]);
       }
     }
 #pragma unroll
@@ -332,11 +335,11 @@ void gemm_planes_kernel(const GemmArgs p) {
       if constexpr (!BKM) {
         f.b0[j] = *reinterpret_cast<const bf16x8_t*>(sb + b_frag[j]);
         f.b1[j] = *reinterpret_cast<const bf16x8_t*>(sb + B_PLANE + b_frag[j]);
-        f.b2[j] = *reinterpret_cast<const bf16x8_t*>(sb + 2 * B_PLANE + b_frag[j]);
+        if constexpr (NP == 3) f.b2[j] = *reinterpret_cast<const bf16x8_t*>(sb + 2 * B_PLANE + b_frag[j]);
       } else {
         f.b0[j] = tr_read(sb + b_frag[j]);
         f.b1[j] = tr_read(sb + B_PLANE + b_frag[j]);
-        f.b2[j] = tr_read(sb + 2 * B_PLANE + b_frag[j]);
+        if constexpr (NP == 3) f.b2[j] = tr_read(sb + 2 * B_PLANE + b_frag[j]);
       }
     }
   };
@@ -355,9 +358,9 @@ void gemm_planes_kernel(const GemmArgs p) {
     if (MT_PLANES_ABLATE & 16) {                     // keep the fragments live without the matrix pipe
       float z = 0.f;
 #pragma unroll
-      for (int i = 0; i < TM; ++i) z += (float)f.a0[i][0] + (float)f.a1[i][1] + (float)f.a2[i][2];
+      for (int i = 0; i < TM; ++i) { z += (float)f.a0[i][0] + (float)f.a1[i][1]; if constexpr (NP == 3) z += (float)f.a2[i][2]; }
 #pragma unroll
-      for (int j = 0; j < TN; ++j) z += (float)f.b0[j][0] + (float)f.b1[j][1] + (float)f.b2[j][2];
+      for (int j = 0; j < TN; ++j) { z += (float)f.b0[j][0] + (float)f.b1[j][1]; if constexpr (NP == 3) z += (float)f.b2[j][2]; }
       acc[0][0][0] += z;
       return;
     }
@@ -369,15 +372,16 @@ void gemm_planes_kernel(const GemmArgs p) {
       nacc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.X[i], f.Y[j], nacc[i][j], 0, 0, 0);
     if constexpr (PHASE) {
 #pragma unroll
-      for (int i = 0; i < TM; ++i) { negate(f.a0[i], phase_mask); negate(f.a1[i], phase_mask); negate(f.a2[i], phase_mask); }
+      for (int i = 0; i < TM; ++i) { negate(f.a0[i], phase_mask); negate(f.a1[i], phase_mask); if constexpr (NP == 3) negate(f.a2[i], phase_mask); }
     }
     if constexpr (ODD) {                              // odd k-steps feed -x0: their a0 products build the negated sum (gemm_split.hpp: BAL)
 #pragma unroll
       for (int i = 0; i < TM; ++i) negate(f.a0[i], 0x80008000u);
-      MT_TERM(a2, b0) MT_TERM(a1, b1) MT_NTERM(a0, b2)
+      // (two pieces: both a0 products go to nacc, a1 b0 stays in acc on every step -- gemm_split.hpp's X6 = false order)
+      if constexpr (NP == 3) { MT_TERM(a2, b0) MT_TERM(a1, b1) MT_NTERM(a0, b2) }
       MT_TERM(a1, b0) MT_NTERM(a0, b1) MT_NTERM(a0, b0)
     } else {
-      MT_TERM(a2, b0) MT_TERM(a1, b1) MT_TERM(a0, b2)
+      if constexpr (NP == 3) { MT_TERM(a2, b0) MT_TERM(a1, b1) MT_TERM(a0, b2) }
       MT_TERM(a1, b0) MT_TERM(a0, b1) MT_TERM(a0, b0)
     }
 #undef MT_TERM

@@ -67,13 +67,14 @@ void gemm_split_kernel(const GemmArgs p) {
   constexpr int BN = WAVES_N * TN * 32;
   constexpr int BK = 16;
   constexpr int A_PLANE = BM * 32, B_PLANE = BN * 32;           // bytes
-  constexpr int STAGE = 3 * (A_PLANE + B_PLANE);
+  constexpr int NP = X6 ? 3 : 2;                                // planes per operand and stage (X6 = false: x0, x1 only)
+  constexpr int STAGE = NP * (A_PLANE + B_PLANE);
   constexpr int AG = (BM * 2 + NT - 1) / NT, BG = (BN * 2 + NT - 1) / NT;   // 8-k granules per thread
   constexpr bool A_ALL = (BM * 2) % NT == 0, B_ALL = (BN * 2) % NT == 0;   // every thread stages AG / BG granules (no predicate)
   constexpr int AG2 = BNB ? 2 * AG : AG;            // staging granules for A (+ A2)
   // LDS map.  Staged B: two stages of {A planes, B planes}.  B planes by DMA: two A stages, then a ring of three B stages.
   constexpr int A_STAGE = BPL ? 3 * A_PLANE : STAGE;             // byte distance between the two A stages
-  constexpr int B_BASE = BPL ? 6 * A_PLANE : 3 * A_PLANE;        // first B stage
+  constexpr int B_BASE = BPL ? 6 * A_PLANE : NP * A_PLANE;       // first B stage
   constexpr int B_STAGE = BPL ? 3 * B_PLANE : STAGE;
   constexpr int LDS_END = BPL ? 6 * A_PLANE + 9 * B_PLANE : 2 * STAGE;
   constexpr int BI = BPL ? (6 * BN / 64) / NW : 1;               // DMA wave-instructions per wave per B tile (3 planes x BN rows x 2 slots)
@@ -358,9 +359,9 @@ void gemm_split_kernel(const GemmArgs p) {
       if (!B_ALL && !b_on[j]) continue;
       bf16x8_t x0, x1, x2;
       split_bf16<X6>(reinterpret_cast<const float(&)[4]>(gb[j][0]), reinterpret_cast<const float(&)[4]>(gb[j][4]), x0, x1, x2);
-      *reinterpret_cast<bf16x8_t*>(st + 3 * A_PLANE + b_dst[j]) = x0;
-      *reinterpret_cast<bf16x8_t*>(st + 3 * A_PLANE + B_PLANE + b_dst[j]) = x1;
-      if constexpr (X6) *reinterpret_cast<bf16x8_t*>(st + 3 * A_PLANE + 2 * B_PLANE + b_dst[j]) = x2;
+      *reinterpret_cast<bf16x8_t*>(st + NP * A_PLANE + b_dst[j]) = x0;
+      *reinterpret_cast<bf16x8_t*>(st + NP * A_PLANE + B_PLANE + b_dst[j]) = x1;
+      if constexpr (X6) *reinterpret_cast<bf16x8_t*>(st + NP * A_PLANE + 2 * B_PLANE + b_dst[j]) = x2;
     }
   };
 

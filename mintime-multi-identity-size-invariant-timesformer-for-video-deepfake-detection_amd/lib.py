@@ -73,6 +73,8 @@ PROTOTYPES = {
     "mt_gemm": [C.POINTER(GemmDesc), C.c_void_p],
     "mt_gemm_set_split": [C.c_int],
     "mt_gemm_get_split": [],
+    "mt_gemm_set_precision": [C.c_int],
+    "mt_gemm_get_precision": [],
     "mt_split_planes": [f32p, C.c_void_p, C.c_int64, C.c_void_p],
     "mt_planes_elems": [C.c_int, C.c_int],
     "mt_split_planes_blk": [f32p, i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
@@ -208,7 +210,7 @@ def build(verbose: bool = False):
 
 # MT_VERSION of include/mintime_hip.h this binding was written against (tests/test_host_logic.py keeps the two equal; the package
 # itself does not need the header at run time -- it may be copied or installed without the repository's include/ directory)
-ABI_VERSION = 121
+ABI_VERSION = 122
 
 
 def header_version() -> int:
@@ -258,6 +260,46 @@ def set_gemm_split(on: bool) -> bool:
     """Select the matrix pipe of the prologue-free contractions (include/mintime_hip.h, mt_gemm_set_split): True = split-operand
     fp32 on the bf16 pipe (default), False = fp32 MFMA everywhere.  Returns the previous setting."""
     return bool(get().mt_gemm_set_split(1 if on else 0))
+
+
+PRECISION_LEVELS = {"highest": 0, "high": 1}        # MT_PRECISION_HIGHEST, MT_PRECISION_HIGH (include/mintime_hip.h)
+_PRECISION_NAMES = {v: k for k, v in PRECISION_LEVELS.items()}
+
+
+def set_matmul_precision(name: str) -> str:
+    """Arithmetic tier of the bf16-pipe contractions (include/mintime_hip.h, mt_gemm_set_precision): "highest" (default) = six piece
+    products, fp32-level error; "high" = three piece products ("bf16x3", about 16 mantissa bits per operand) at half the matrix
+    instructions.  Process-wide, read when a call is dispatched -- also by a replayed launch plan.  Returns the previous name.
+    torch.get_float32_matmul_precision() is NOT followed; mirror it with set_matmul_precision(torch.get_float32_matmul_precision())."""
+    if name not in PRECISION_LEVELS:
+        raise MintimeHipError(f"set_matmul_precision: {name!r} is not one of {sorted(PRECISION_LEVELS)} (no one-product tier exists)")
+    prev = get().mt_gemm_set_precision(PRECISION_LEVELS[name])
+    if prev < 0:
+        check(prev, "mt_gemm_set_precision")
+    return _PRECISION_NAMES[prev]
+
+
+def get_matmul_precision() -> str:
+    return _PRECISION_NAMES[get().mt_gemm_get_precision()]
+
+
+class matmul_precision:
+    """Context manager: `with matmul_precision("high"): ...` runs the block at that tier and restores the previous one on exit,
+    also when the block raises."""
+
+    def __init__(self, name: str):
+        if name not in PRECISION_LEVELS:
+            raise MintimeHipError(f"matmul_precision: {name!r} is not one of {sorted(PRECISION_LEVELS)}")
+        self.name = name
+        self.prev = None
+
+    def __enter__(self):
+        self.prev = set_matmul_precision(self.name)
+        return self
+
+    def __exit__(self, *exc):
+        set_matmul_precision(self.prev)
+        return False
 
 
 def split_planes(w):
