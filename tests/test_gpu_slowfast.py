@@ -80,10 +80,26 @@ def _to_ncdhw(fm, C=None):
     return t.permute(0, 4, 1, 2, 3)
 
 
+# odd spatial sizes through the stride-2 convolutions: (name, cin, cout, kernel, stride, padding) at N = 1, (T, H, W) = (4, 7, 9)
+ODD_CONVS = [
+    ("conv_b_s2", 16, 16, (1, 3, 3), (1, 2, 2), (0, 1, 1)),
+    ("branch1_s2", 32, 64, (1, 1, 1), (1, 2, 2), (0, 0, 0)),
+    ("stem_slow", 3, 64, (1, 7, 7), (1, 2, 2), (0, 3, 3)),
+]
+
+
 @pytest.mark.parametrize("name,cin,cout,k,s,p", CONVS, ids=[c[0] for c in CONVS])
 def test_conv3d_fwd_dgrad_wgrad(name, cin, cout, k, s, p):
+    _conv_case(name, cin, cout, k, s, p, 2, (16 if name in ("stem_fast", "fusion") else 4), 18, 14)
+
+
+@pytest.mark.parametrize("name,cin,cout,k,s,p", ODD_CONVS, ids=[c[0] for c in ODD_CONVS])
+def test_conv3d_fwd_dgrad_wgrad_odd_sizes(name, cin, cout, k, s, p):
+    _conv_case(name, cin, cout, k, s, p, 1, 4, 7, 9)
+
+
+def _conv_case(name, cin, cout, k, s, p, N, T, H, W):
     torch.manual_seed(1)
-    N, T, H, W = 2, (16 if name in ("stem_fast", "fusion") else 4), 18, 14
     x = torch.randn(N, cin, T, H, W).double()                 # fp32 values: the device sees the same operands
     w = (torch.randn(cout, cin, *k) / (cin * k[0] * k[1] * k[2]) ** 0.5).double()
     stem = cin == 3
@@ -117,7 +133,7 @@ def test_conv3d_fwd_dgrad_wgrad(name, cin, cout, k, s, p):
         E.conv_dgrad(xf, dz, w.float().to(dev), conv, gx, False)
         e_d = rel_err(_to_ncdhw(E.Fm(gx, N, T, H, W)), xg.grad)
     torch.cuda.synchronize()
-    print(f"conv {name}: fwd {e_fwd:.2e} stats {e_st:.2e} wgrad {e_w:.2e} dgrad {e_d:.2e}")
+    print(f"conv {name} {(N, T, H, W)}: fwd {e_fwd:.2e} stats {e_st:.2e} wgrad {e_w:.2e} dgrad {e_d:.2e}")
     assert e_fwd <= CONV_TOL and e_st <= CONV_TOL and e_w <= CONV_TOL and e_d <= CONV_TOL, (e_fwd, e_st, e_w, e_d)
 
 
