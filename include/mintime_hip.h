@@ -221,7 +221,8 @@ int mt_layernorm_fwd(const float* x, const float* gamma, const float* beta, floa
                      int rows, int dim, float eps, void* y_planes, void* stream);
 
 /* cls token + positional + size embeddings (:231-248), in place on x [B, 1+F*n, dim] whose rows 1.. hold the
- * patch-embedding output.  positions int64 [B,1+F*n]; sizes int32 [B,F] (NULL size_emb: enable-size-emb False). */
+ * patch-embedding output.  positions int64 [B,1+F*n] (NULL: the token index); sizes int32 [B,F] (NULL size_emb: enable-size-emb False -- sizes is then not read,
+ * whatever it holds). */
 int mt_embed_fwd(float* x, const float* cls, const float* pos_emb, const float* size_emb,
                  const int64_t* positions, const int32_t* sizes, int B, int F, int n, int dim, int pos_rows, int size_rows,
                  int* err_flag, void* stream);
@@ -372,7 +373,9 @@ int mt_head_bwd(const float* dlogits, const float* x, const float* gamma, const 
 int mt_embed_bwd(const float* dx, float* dcls, float* dpos_emb, float* dsize_emb, const int64_t* positions,
                  const int32_t* sizes, int B, int F, int n, int dim, int pos_rows, int size_rows, void* stream);
 
-/* adjoint of mt_attn_fwd: dout [B,N,H*64] -> dqkv [B,N,3*H*64] (fully written). Probabilities are recomputed from qkv.
+/* adjoint of mt_attn_fwd: dout [B,N,H*64] -> dqkv [B,N,3*H*64] (modes 0 / 1: fully written). Probabilities are recomputed from qkv.
+ * mode 2 reads row 0 of dout only and writes dk / dv of every row and dq of row 0 of each clip; the dq section (columns [0, H*64)) of
+ * the patch rows is NOT written and keeps what it held -- a caller that reads it zero-fills it first.
  * dqkv_planes (optional, mode 0 / 1): the result as a plane tensor [B*N][3*H*64] (operand of the QKV layer's data and weight
  * gradients).  dqkv is then working memory: its patch rows are left holding the cls query's contribution only. */
 int mt_attn_bwd(const float* qkv, const float* dout, float* dqkv, const uint8_t* mask, const uint8_t* ident,

@@ -55,7 +55,7 @@ int det_release(hipStream_t s) {
 // ---- log reduce: block (g, chunk of W outputs); 256 threads = (256 / W) rank segments x W outputs
 template <typename OUT, int W>
 __global__ __launch_bounds__(256) void det_reduce_kernel(const float* __restrict__ vals, const int* __restrict__ base, int R, int P,
-                                                         OUT* __restrict__ out, int g0) {
+                                                         OUT* __restrict__ out, int g0, int64_t limit) {
   __shared__ double part[256];
   const int g = g0 + blockIdx.x, j = blockIdx.y * W + (threadIdx.x % W), seg = threadIdx.x / W;
   constexpr int SEGS = 256 / W;
@@ -79,16 +79,16 @@ __global__ __launch_bounds__(256) void det_reduce_kernel(const float* __restrict
     double t = part[threadIdx.x];
 #pragma unroll
     for (int q = 1; q < SEGS; ++q) t += part[q * W + threadIdx.x];
-    out[(int64_t)b + j] += (OUT)t;
+    if (limit < 0 || (int64_t)b + j < limit) out[(int64_t)b + j] += (OUT)t;
   }
 }
 
 template <typename OUT>
-static int launch_reduce(const DetLog& L, int G, OUT* out, int g0, int count, hipStream_t s) {
+static int launch_reduce(const DetLog& L, int G, OUT* out, int g0, int count, int64_t limit, hipStream_t s) {
   if (count < 0) count = G - g0;
   if (count <= 0 || !out) return 0;
-  if (L.P <= 16) hipLaunchKernelGGL((det_reduce_kernel<OUT, 16>), dim3(count, (L.P + 15) / 16), dim3(256), 0, s, L.vals, L.base, L.R, L.P, out, g0);
-  else hipLaunchKernelGGL((det_reduce_kernel<OUT, 64>), dim3(count, (L.P + 63) / 64), dim3(256), 0, s, L.vals, L.base, L.R, L.P, out, g0);
+  if (L.P <= 16) hipLaunchKernelGGL((det_reduce_kernel<OUT, 16>), dim3(count, (L.P + 15) / 16), dim3(256), 0, s, L.vals, L.base, L.R, L.P, out, g0, limit);
+  else hipLaunchKernelGGL((det_reduce_kernel<OUT, 64>), dim3(count, (L.P + 63) / 64), dim3(256), 0, s, L.vals, L.base, L.R, L.P, out, g0, limit);
   return check_launch("det_reduce");
 }
 
@@ -106,8 +106,8 @@ DetScope::DetScope(hipStream_t stream, int groups, int ranks, int p, bool enable
   on = true;
 }
 static int no_arena() { return fail(MT_ERR_LAUNCH, "deterministic mode: no workspace for the partial-sum log (hipMalloc failed, or the workspace would have to grow under stream capture)"); }
-int DetScope::reduce_f32(float* out, int g0, int count) { return failed ? no_arena() : (on ? launch_reduce<float>(log, G, out, g0, count, s) : 0); }
-int DetScope::reduce_f64(double* out, int g0, int count) { return failed ? no_arena() : (on ? launch_reduce<double>(log, G, out, g0, count, s) : 0); }
+int DetScope::reduce_f32(float* out, int g0, int count, int64_t limit) { return failed ? no_arena() : (on ? launch_reduce<float>(log, G, out, g0, count, limit, s) : 0); }
+int DetScope::reduce_f64(double* out, int g0, int count) { return failed ? no_arena() : (on ? launch_reduce<double>(log, G, out, g0, count, -1, s) : 0); }
 
 // ---- split-K slabs
 __global__ __launch_bounds__(256) void det_slab_reduce_kernel(float* __restrict__ C, int64_t ldc, const float* __restrict__ ws, int splits,
@@ -174,7 +174,7 @@ int det_gemm_finish(hipStream_t s, bool launched) {
   tl_log = LogPending();
   if (!launched) return 0;
   if (l.on)
-    if (int rc = launch_reduce<float>(l.log, l.G, l.out, 0, -1, s)) return rc;
+    if (int rc = launch_reduce<float>(l.log, l.G, l.out, 0, -1, -1, s)) return rc;
   if (!q.ws) return 0;
   return det_slab_reduce(q.C, q.ldc, q.ws, q.splits, q.M, q.N, s);
 }

@@ -38,8 +38,9 @@ struct DetScope {
   bool failed;        // the switch is on but the arena could not be had: the kernel fell back to atomics, reduce_* reports it
   // base_zero: every group's output offset is 0 (the kernel need not write it; reduce group ranges into different targets)
   DetScope(hipStream_t stream, int groups, int ranks, int p, bool enable = true, bool base_zero = false);
-  // out[base[g] + j] += sum_r vals[g][r][j]   (r ascending, fp64 accumulator); groups [g0, g0 + count), count < 0 = all
-  int reduce_f32(float* out, int g0 = 0, int count = -1);
+  // out[base[g] + j] += sum_r vals[g][r][j]   (r ascending, fp64 accumulator); groups [g0, g0 + count), count < 0 = all;
+  // limit >= 0: out has `limit` elements and the last group reaches past them (P does not divide the target): those are left alone
+  int reduce_f32(float* out, int g0 = 0, int count = -1, int64_t limit = -1);
   int reduce_f64(double* out, int g0 = 0, int count = -1);
 };
 

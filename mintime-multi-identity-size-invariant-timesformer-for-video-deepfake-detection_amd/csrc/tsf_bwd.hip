@@ -1634,7 +1634,7 @@ extern "C" int mt_colsum(const float* A, int64_t lda, mt_rowmap map, int M, int 
   hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64, (M + rpb - 1) / rpb), dim3(256), 0, (hipStream_t)stream, A, lda, map.gin,
                      map.gout, map.off, M, N, out, rpb, det.log);
   const int rc = check_launch("mt_colsum");
-  return rc ? rc : det.reduce_f32(out);
+  return rc ? rc : det.reduce_f32(out, 0, -1, N);     // the last 64-column group may reach past out[N)
 }
 
 extern "C" int mt_head_bwd(const float* dlogits, const float* x, const float* gamma, const float* beta, const float* w,

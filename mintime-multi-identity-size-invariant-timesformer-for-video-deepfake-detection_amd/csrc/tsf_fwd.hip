@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(float* __restrict__ x, c
   const int b = row / N, t = row - b * N;
   int64_t pi = positions ? positions[row] : (int64_t)t;
   int si = 0;
-  if (t > 0 && sizes) si = sizes[b * F + (t - 1) / n];
+  if (t > 0 && sizes && size_emb) si = sizes[b * F + (t - 1) / n];     // no size table (enable-size-emb False): the buckets are not looked at
   // nn.Embedding raises on an out-of-range index; here the access is clamped into the table and a sticky flag is raised
   if (pi < 0 || pi >= pos_rows || si < 0 || si >= size_rows) {
     if (err && lane == 0) atomicOr(err, (pi < 0 || pi >= pos_rows) ? 1 : 2);
