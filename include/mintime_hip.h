@@ -438,6 +438,18 @@ int mt_stem_conv_wgrad(const float* du, const float* z, const float* kabc, const
 int mt_stem_conv_wgrad_valid(const float* du, const float* z, const float* kabc, const void* x, int x_is_u8, float* dw, int N,
                              int H, int W, void* stream);
 
+/* _conv_stem data gradient = the gradient w.r.t. the crops (replaces torch autograd through _conv_stem, reference
+ * efficientnet_pytorch/model.py:173,276): dx [N,H,W,3] fp32, OVERWRITTEN (every element is written);
+ * dx[n,ih,iw,ci] = sum_{kh,kw,co} dz[n,oh,ow,co] * w[co,ci,kh,kw] over the taps with ih+pb-kh = 2 oh, iw+pb-kw = 2 ow, dz = ka*du+kb*z+kc,
+ * pb = the forward's leading TF-SAME pad.  du, z [N*Ho*Wo,32] 16-byte aligned, kabc [3][32], w [32,3,3,3].  Limits as mt_stem_conv_fwd:
+ * W <= 512, H and W need the same leading pad.  One writer per element, no atomics: bit-identical from run to run. */
+int mt_stem_conv_dgrad(const float* du, const float* z, const float* kabc, const float* w, float* dx, int N, int H, int W,
+                       void* stream);
+/* ... of the unpadded stride-2 3x3 convolution (replaces torch autograd through Xception's conv1, reference xception.py:161-170);
+ * du, z [N,(H-3)/2+1,(W-3)/2+1,32], H, W >= 3.  Input rows / columns that no tap reaches (the last one of an even H / W) come out 0. */
+int mt_stem_conv_dgrad_valid(const float* du, const float* z, const float* kabc, const float* w, float* dx, int N, int H, int W,
+                             void* stream);
+
 /* Weight gradient of a 1x1 convolution with few channels and very many rows (MBConv expand / project convs of stages 1-4,
  * efficientnet_pytorch/model.py:93-104 under train.py:371):  dw[Cout,Cin] += sum_r (ka*du+kb*z+kc)[r,Cout] * a[r,Cin] with
  * a = x, or (gate != NULL) swish(sc*x+sh)*gate[r/hw].  The whole (32-padded) result stays in MFMA accumulators while the rows

@@ -71,6 +71,14 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
                  default=len(blocks))
     if any(need[:3]):
         lowest = -1                                                             # the stem itself is trainable
+    if need_dx:
+        # gradient w.r.t. the crops: the walk reaches the stem whatever is frozen (every block hands its data gradient down; the
+        # frozen weight-gradient launches stay skipped)
+        lowest = -1
+        need_below = [True] * len(blocks)
+        if W > 512:
+            raise NotImplementedError("gradient w.r.t. the input crops: mt_stem_conv_dgrad takes crops of at most 512 columns")
+    dx = None
     run = {"blocks_run": 0, "wgrad_launches": 0, "stem_run": False}
     total_c = arch.STEM_COUT + arch.HEAD_COUT + sum((b.spec.cexp if b.spec.has_expand else 0) + b.spec.cexp + b.spec.cout
                                                     for b in blocks)
@@ -325,6 +333,11 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
                 run["wgrad_launches"] += 1
                 L.check(lib.mt_stem_conv_wgrad(L.ptr(du_in), L.ptr(stem["z"]), L.ptr(kabc0), L.ptr(stem["x"]), 1 if stem["x"].dtype == torch.uint8 else 0, L.ptr(grads[0]), N, H, W, st),
                         "mt_stem_conv_wgrad")
+            if need_dx:
+                # the last operator of the walk: the transposed stem convolution, 32 -> 3 channels (csrc/stem_dgrad.hip)
+                dx = _new(dev, N, H, W, 3)
+                L.check(lib.mt_stem_conv_dgrad(L.ptr(du_in), L.ptr(stem["z"]), L.ptr(kabc0), L.ptr(P[0]), L.ptr(dx), N, H, W, st),
+                        "mt_stem_conv_dgrad")
             dy = None
         del du_in
         if not keep_saved:
@@ -332,12 +345,9 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
         side.release_point()
 
     side.wait()
-    if need_dx:
-        raise NotImplementedError("gradient w.r.t. the input crops is not part of the MINTIME training path "
-                                  "(train.py never sets requires_grad on videos)")
     LAST_RUN.update(run)
     if plan is not None:
         plan.extra.update(flat_grads=flat_grads, last_run=dict(LAST_RUN))       # (a replay restores LAST_RUN)
     L.grads_ready(model, params, flat_grads)
     out = [g if nd else None for nd, g in zip(need_dparams, grads)]
-    return None, out
+    return dx, out

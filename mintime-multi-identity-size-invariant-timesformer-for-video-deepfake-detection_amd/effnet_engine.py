@@ -345,7 +345,8 @@ class _EffNetFunction(torch.autograd.Function):
         ctx.shape = (N, H, W)
         ctx.model, ctx.params, ctx.training = model, params, model.training
         stream = key = state = None
-        if save and not want_blocks:
+        # (crops that require grad -- saliency, adversarial examples -- run the eager launch sequence: plan keys do not carry them)
+        if save and not want_blocks and not ctx.needs_input_grad[2]:
             stream = torch.cuda.current_stream(x_nhwc.device).cuda_stream
             state = list(params) + list(model.buffers())       # (what a recording holds the addresses of)
             key = ("ef", tuple(x_nhwc.shape), x_nhwc.dtype, model.training, L.deterministic(), L.gemm_split_enabled(),

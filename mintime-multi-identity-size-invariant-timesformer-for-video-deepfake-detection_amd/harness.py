@@ -145,6 +145,32 @@ def baseline_eval_step(ex, model, batch):
     return baseline_forward(ex, model, batch)
 
 
+def input_gradient(ex, model, batch, pos_weight=None):
+    """Gradient of the callers' loss with respect to the face crops: what saliency maps and FGSM / PGD perturbations are made of.
+    ex: EfficientNet-B0 or Xception; model: SizeInvariantTimeSformer (forward() above) or Baseline (baseline_forward()).
+    Returns (logits, loss, dvideos) with dvideos.shape == batch["videos"].shape, fp32; nothing is added to any parameter's .grad.
+    The modules run in the mode they are in (the saliency setting is eval() with every parameter requires_grad_(False); parameters
+    that do require grad only cost their weight-gradient launches, and a train-mode extractor updates its BatchNorm running statistics
+    as any forward does).  The extractor runs its eager launch sequence: recorded launch plans are neither used nor made.
+    uint8 crops have no gradient: cast them first (`videos.float()`)."""
+    videos = batch["videos"]
+    if not torch.is_tensor(videos) or not videos.is_floating_point():
+        raise ValueError(f"input_gradient: videos must be a floating-point tensor (got {getattr(videos, 'dtype', type(videos))}); "
+                         "cast uint8 crops with .float() first")
+    if not videos.is_cuda:
+        raise ValueError("input_gradient: videos must be on the device (the extractors have no CPU path)")
+    if not isinstance(model, (SizeInvariantTimeSformer, Baseline)):
+        raise TypeError(f"input_gradient: model must be a SizeInvariantTimeSformer or a Baseline, got {type(model).__name__}")
+    x = videos.detach().requires_grad_(True)
+    local = dict(batch, videos=x)
+    with torch.enable_grad():
+        y_pred = baseline_forward(ex, model, local) if isinstance(model, Baseline) else forward(ex, model, local)
+        logits = y_pred[0] if isinstance(y_pred, tuple) else y_pred
+        loss = optim.bce_with_logits(logits, batch["labels"], pos_weight)
+        dvideos, = torch.autograd.grad(loss, x)
+    return logits.detach(), loss.detach(), dvideos
+
+
 def build_slowfast(seed=0, device="cuda", head_pool_kernel_sizes=((8, 7, 7), (32, 7, 7)), num_classes=1):
     """`--model 2` (train.py:143-147): slowfast_r50 with blocks[6].proj = nn.Linear(2304, num_classes), on the device, train mode.
     Returns (model, optimizer): SGD(lr, weight_decay) of config/slowfast.yaml through optim.FusedSGD."""

@@ -155,6 +155,8 @@ PROTOTYPES = {
     "mt_conv1x1_bwd_fused": [f32p] * 7 + [C.c_int64, C.c_int, C.c_int, C.c_void_p],
     "mt_stem_conv_wgrad": [f32p] * 4 + [C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "mt_stem_conv_wgrad_valid": [f32p] * 4 + [C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "mt_stem_conv_dgrad": [f32p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "mt_stem_conv_dgrad_valid": [f32p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_void_p],
     "mt_bn_act_fwd_planes": [f32p, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_void_p, C.c_void_p],
     "mt_bn_swish_gate_planes": [f32p, f32p, f32p, f32p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "mt_baseline_head_fwd": [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [f32p] * 8 + [C.c_void_p],

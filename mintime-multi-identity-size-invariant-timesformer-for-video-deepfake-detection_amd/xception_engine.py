@@ -277,9 +277,10 @@ def xception_forward(model, x, params, training, save, plan=None):
     return feat, saved, cur.H
 
 
-def xception_backward(model, params, saved, shape, training, dfeat, need_dparams, keep_saved=False, plan=None):
-    """keep_saved: the activation records belong to a launch plan (plans.py) and stay for its next replay; plan: the NetPlan whose
-    backward phase is being recorded (it keeps the flat gradient buffer)."""
+def xception_backward(model, params, saved, shape, training, dfeat, need_dparams, keep_saved=False, plan=None, need_dx=False):
+    """Returns (gradient w.r.t. the crops [N,H,W,3] or None, parameter gradients).  keep_saved: the activation records belong to a
+    launch plan (plans.py) and stay for its next replay; plan: the NetPlan whose backward phase is being recorded (it keeps the flat
+    gradient buffer); need_dx: the crops require grad (the walk ends with mt_stem_conv_dgrad_valid)."""
     lib = L.get()
     dev = dfeat.device
     N, H, W = shape
@@ -467,6 +468,15 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
     L.gemm(L.OP_NT, dz2, wp2t, da1, M1, 32, 576, 576, 576, 32, prologue=L.PRO_IM2COL, conv=(H2, H2, 64, H1, H1, 3, 1, 2, NONE))
     du1 = _new(dev, M1, 32)
     k1 = bn_kabc(bn1, bn_sums(da1, z1, bn1, M1, act=RELU, dout=du1), 1, du1, z1, M1)
+    dx = None
+    if need_dx:
+        if not (XC_STEM and W <= 512):
+            raise NotImplementedError("gradient w.r.t. the input crops: mt_stem_conv_dgrad_valid takes crops of at most 512 columns "
+                                      "and needs MT_XC_STEM=1")
+        # the last operator of the walk: the transposed conv1, 32 -> 3 channels (csrc/stem_dgrad.hip)
+        dx = _new(dev, N, H, W, 3)
+        L.check(lib.mt_stem_conv_dgrad_valid(L.ptr(du1), L.ptr(z1), L.ptr(k1), L.ptr(P[0]), L.ptr(dx), N, H, W, L.stream_ptr()),
+                "mt_stem_conv_dgrad_valid")
     if XC_STEM and W <= 512:
         L.check(lib.mt_stem_conv_wgrad_valid(L.ptr(du1), L.ptr(z1), L.ptr(k1), L.ptr(saved["x"]), 1 if saved["x"].dtype == torch.uint8 else 0,
                                              L.ptr(grads[0]), N, H, W, L.stream_ptr()), "mt_stem_conv_wgrad_valid")
@@ -483,7 +493,7 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
     if plan is not None:
         plan.extra["flat_grads"] = flat_grads
     L.grads_ready(model, P, flat_grads)
-    return [g_ if need else None for need, g_ in zip(need_dparams, grads)]
+    return dx, [g_ if need else None for need, g_ in zip(need_dparams, grads)]
 
 
 def _plannable():
@@ -507,7 +517,8 @@ class _XceptionFunction(torch.autograd.Function):
         ctx.shape = (N, H, W)
         ctx.model, ctx.params, ctx.training = model, params, model.training
         stream = key = state = None
-        if save and _plannable() and W <= 512 and L.gemm_split_enabled():
+        # (crops that require grad run the eager launch sequence: plan keys do not carry them)
+        if save and _plannable() and W <= 512 and L.gemm_split_enabled() and not ctx.needs_input_grad[1]:
             stream = torch.cuda.current_stream(x_nhwc.device).cuda_stream
             state = list(params) + list(model.buffers())       # (what a recording holds the addresses of)
             key = ("xc", tuple(x_nhwc.shape), x_nhwc.dtype, model.training, L.deterministic(), tuple(ctx.needs_input_grad[2:]), stream,
@@ -521,13 +532,11 @@ class _XceptionFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dfeat):
-        if ctx.needs_input_grad[1]:
-            raise NotImplementedError("gradient w.r.t. the input crops is not part of the MINTIME training path")
-
         def body(g, keep_saved, plan):
-            return (), xception_backward(ctx.model, ctx.params, ctx.saved, ctx.shape, ctx.training, g, ctx.needs_input_grad[2:],
-                                         keep_saved=keep_saved, plan=plan)
-        return (None, None) + plans.backward(ctx, "Xception", dfeat.contiguous(), body)
+            dx, dparams = xception_backward(ctx.model, ctx.params, ctx.saved, ctx.shape, ctx.training, g, ctx.needs_input_grad[2:],
+                                            keep_saved=keep_saved, plan=plan, need_dx=ctx.needs_input_grad[1])
+            return (dx,), dparams
+        return (None,) + plans.backward(ctx, "Xception", dfeat.contiguous(), body)
 
 
 def xception_apply(model, inputs):
