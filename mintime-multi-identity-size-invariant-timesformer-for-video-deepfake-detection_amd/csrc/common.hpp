@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -21,6 +22,14 @@ inline int fail(int code, const char* fmt, ...) {
   va_end(ap);
   return code;
 }
+
+// The integer knobs of the environment: the value of `name`, or `dflt` when it is not set ...
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+// ... and the switches that are on when set to anything, "0" included
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }
 
 inline int cur_device() {
   int d = 0;

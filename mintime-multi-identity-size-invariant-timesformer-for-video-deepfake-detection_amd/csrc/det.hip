@@ -8,7 +8,7 @@
 namespace mt {
 
 static std::atomic<int>& det_flag() {
-  static std::atomic<int> f{getenv("MT_DETERMINISTIC") ? atoi(getenv("MT_DETERMINISTIC")) != 0 : 0};
+  static std::atomic<int> f{env_int("MT_DETERMINISTIC", 0) != 0};
   return f;
 }
 int det_enabled() { return det_flag().load(std::memory_order_relaxed); }

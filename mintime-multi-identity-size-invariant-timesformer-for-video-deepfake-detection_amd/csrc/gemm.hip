@@ -2,8 +2,8 @@
 #include "../../include/mintime_hip.h"
 #include "common.hpp"
 #include "gemm_core.hpp"
+#include "gemm_geometry.hpp"
 #include "det.hpp"
-#include <stdlib.h>
 
 using namespace mt;
 
@@ -27,7 +27,7 @@ constexpr Cfg kCfg[6] = {{128, 128, 256}, {128, 64, 256}, {256, 32, 256}, {64, 6
 int pick_cfg(int op, int M, int N, int prologue, int epilogue) {
   (void)prologue;
   if (epilogue == MT_EPI_GEGLU) return CFG_BIG;
-  if (const char* f = getenv("MT_FORCE_CFG")) return atoi(f);   // tuning experiments only
+  if (env_set("MT_FORCE_CFG")) return env_int("MT_FORCE_CFG", 0);   // tuning experiments only
   if (N <= 32) return CFG_NARROW;
   if (epilogue == MT_EPI_GEGLU_BWD) return CFG_SMALL;
   if (op != MT_OP_TN && M >= 4096 && N >= 128 && (int64_t)((M + 127) / 128) * ((N + 127) / 128) <= 768) return CFG_SMALL;
@@ -77,6 +77,15 @@ namespace mt { int try_launch_split(const mt_gemm_desc* d, GemmArgs a, hipStream
 static long long* g_trace = nullptr;
 // tuning aid, not part of the ABI header: per-block phase timestamps of the following mt_gemm launches (NULL = off)
 extern "C" void mt_debug_gemm_trace(long long* buf) { g_trace = buf; }
+// test aids, not part of the ABI header either: the launch geometry (gemm_geometry.hpp) as plain integers; they launch nothing
+extern "C" void mt_debug_tile_grid(int M, int N, int bm, int bn, long long panel_bytes, int* out4) {
+  const TileGrid g = tile_grid(M, N, bm, bn, panel_bytes);
+  out4[0] = g.m_tiles; out4[1] = g.n_tiles; out4[2] = g.grid_x; out4[3] = g.group_n;
+}
+extern "C" void mt_debug_split_k(int K, int tiles, int split_k, int auto_target, int k_round, int form, int* out4) {
+  const SplitK r = split_k_ranges(K, tiles, split_k, auto_target, k_round, (KForm)form);
+  out4[0] = r.k_chunk; out4[1] = r.ranges; out4[2] = r.grid_y; out4[3] = r.xcd_k;
+}
 
 static int gemm_impl(const mt_gemm_desc* d, void* stream) {
   if (!d || !d->A || !d->B || !d->C) return fail(MT_ERR_ARG, "mt_gemm: null pointer");
@@ -150,52 +159,29 @@ static int gemm_impl(const mt_gemm_desc* d, void* stream) {
     if (rc <= 0) return rc;
   }
   int cfg = pick_cfg(d->op, d->M, d->N, d->prologue, d->epilogue);
-  static const int wg64_var = getenv("MT_CONV_WG64") ? atoi(getenv("MT_CONV_WG64")) : 2;      // lab: 0 = the 128 x 64 tile, 1 = six wavefronts
+  static const int wg64_var = env_int("MT_CONV_WG64", 2);      // lab: 0 = the 128 x 64 tile, 1 = six wavefronts
   if (d->op == MT_OP_TN && d->b_prologue == MT_BPRO_IM2COL && d->epilogue == MT_EPI_ATOMIC && d->M <= 64 && d->N > 192 && d->N <= 288 && wg64_var != 0)
     cfg = (det_enabled() || wg64_var == 1) ? CFG_WG64 : CFG_WG64K;   // (deterministic mode writes per-split slabs: one writer per tile)
-  const int m_tiles = (d->M + kCfg[cfg].bm - 1) / kCfg[cfg].bm;
-  const int n_tiles = (d->N + kCfg[cfg].bn - 1) / kCfg[cfg].bn;
-  dim3 grid(m_tiles * n_tiles, 1, 1);
-  a.group_n = 0;
+  const TileGrid tg = tile_grid(d->M, d->N, kCfg[cfg].bm, kCfg[cfg].bn, (int64_t)kCfg[cfg].bn * d->K * 4);
+  dim3 grid(tg.grid_x, 1, 1);
+  a.group_n = tg.group_n;
   a.trace = g_trace;
-  if (m_tiles >= 32 && n_tiles >= 2 && !getenv("MT_NO_L2_BLOCKING")) {
-    // size a column group so its B panels take ~2 MB of the XCD's 4 MB L2
-    const int64_t panel = (int64_t)kCfg[cfg].bn * d->K * 4;
-    int gn = (int)((2 << 20) / (panel > 0 ? panel : 1));
-    if (gn < 1) gn = 1;
-    if (gn > n_tiles) gn = n_tiles;
-    a.group_n = gn;
-    const int max_rows = (m_tiles + 7) / 8;
-    grid.x = 8 * max_rows * n_tiles;
-  }
 
   // im2col prologues: the granule form (gemm_core.hpp) for float images with C % 4 == 0 and k <= 5, else the per-element gather
-  static const bool im_any = getenv("MT_IM2COL_ANY") != nullptr;                  // lab: the per-element gather everywhere
+  static const bool im_any = env_set("MT_IM2COL_ANY");                  // lab: the per-element gather everywhere
   const bool im_granule = (d->conv_C & 3) == 0 && !d->conv_src_u8 && d->conv_k * d->conv_k <= 32 && !im_any;
 #define COMBO(OP, AL, BL, PRO, EPI)                                                        \
   if (d->op == OP && d->prologue == PRO && d->epilogue == EPI)                             \
     return launch<AL, BL, PRO, EPI>(cfg, a, grid, s);
 
   if (d->op == MT_OP_TN) {
-    int splits = d->split_k;
-    if (splits <= 0) {
-      // auto: enough blocks to fill 256 CUs several times over (these outputs are skinny: a handful of tiles), but keep
-      // >= 256 contraction rows per block so the fp32 atomics of the epilogue stay a small fraction of the work
-      const int tiles = m_tiles * n_tiles;
-      static const int target = getenv("MT_WGRAD_BLOCKS_OLD") ? atoi(getenv("MT_WGRAD_BLOCKS_OLD")) : 2048;   // tuning knobs
-      static const int min_rows = getenv("MT_WGRAD_MINROWS_OLD") ? atoi(getenv("MT_WGRAD_MINROWS_OLD")) : 256;
-      splits = (target + tiles - 1) / tiles;
-      const int max_splits = d->K / min_rows > 0 ? d->K / min_rows : 1;
-      if (splits > max_splits) splits = max_splits;
-      if (splits < 1) splits = 1;
-    }
-    int chunk = (d->K + splits - 1) / splits;
-    chunk = (chunk + MT_BK - 1) / MT_BK * MT_BK;
-    splits = (d->K + chunk - 1) / chunk;
-    a.k_chunk = chunk;
-    grid.y = splits;
+    // auto: enough blocks to fill 256 CUs several times over (these outputs are skinny: a handful of tiles)
+    static const int target = env_int("MT_WGRAD_BLOCKS_OLD", 2048);   // tuning knob
+    const SplitK sk = split_k_ranges(d->K, tg.m_tiles * tg.n_tiles, d->split_k, target, MT_BK, K_PLAIN);
+    a.k_chunk = sk.k_chunk;
+    grid.y = sk.grid_y;
     if (d->epilogue == MT_EPI_ATOMIC)
-      if (int rc = det_gemm_setup(a.C, a.ldc, a.det_slab, d->M, d->N, splits, a.c_map.gin != 0, s)) return rc;
+      if (int rc = det_gemm_setup(a.C, a.ldc, a.det_slab, d->M, d->N, sk.ranges, a.c_map.gin != 0, s)) return rc;
     if (d->b_prologue == MT_BPRO_BN_SWISH_GATE) {
       if (d->prologue == MT_PRO_BN_BWD && d->epilogue == MT_EPI_ATOMIC)
         return launch<LAYOUT_KMAJOR, LAYOUT_KMAJOR, PRO_BN_BWD, EPI_ATOMIC, BPRO_BN_SWISH_GATE>(cfg, a, grid, s);
@@ -213,13 +199,10 @@ static int gemm_impl(const mt_gemm_desc* d, void* stream) {
   }
   if (d->epilogue == MT_EPI_ATOMIC && (d->op == MT_OP_NT || d->op == MT_OP_NN)) {
     // split-K with fp32 atomics into a caller-initialised C: evens out the tail of skinny problems (e.g. 396 tiles on 256 CUs)
-    int splits = d->split_k > 0 ? d->split_k : 1;
-    int chunk = (d->K + splits - 1) / splits;
-    chunk = (chunk + MT_BK - 1) / MT_BK * MT_BK;
-    splits = (d->K + chunk - 1) / chunk;
-    a.k_chunk = chunk;
-    grid.y = splits;
-    if (int rc = det_gemm_setup(a.C, a.ldc, a.det_slab, d->M, d->N, splits, a.c_map.gin != 0, s)) return rc;
+    const SplitK sk = split_k_ranges(d->K, tg.m_tiles * tg.n_tiles, d->split_k, 0, MT_BK, K_PLAIN);
+    a.k_chunk = sk.k_chunk;
+    grid.y = sk.grid_y;
+    if (int rc = det_gemm_setup(a.C, a.ldc, a.det_slab, d->M, d->N, sk.ranges, a.c_map.gin != 0, s)) return rc;
     COMBO(MT_OP_NT, LAYOUT_KCONTIG, LAYOUT_KCONTIG, PRO_NONE, EPI_ATOMIC)
     COMBO(MT_OP_NN, LAYOUT_KCONTIG, LAYOUT_KMAJOR, PRO_NONE, EPI_ATOMIC)
     return fail(MT_ERR_UNSUPPORTED, "mt_gemm: split-K atomic epilogue only without prologue");

@@ -4,8 +4,8 @@
 #include "../../include/mintime_hip.h"
 #include "common.hpp"
 #include "gemm_planes_launch.hpp"
+#include "gemm_geometry.hpp"
 #include "det.hpp"
-#include <stdlib.h>
 #include <string.h>
 
 using namespace mt;
@@ -96,8 +96,7 @@ int cu_count() {
 int g_persist = -1;
 int persist_blocks() {
   if (g_persist < 0) {
-    const char* e = getenv("MT_PLANES_PERSIST");
-    g_persist = e ? atoi(e) : 0;
+    g_persist = env_int("MT_PLANES_PERSIST", 0);
     if (g_persist < 0 || g_persist > 4) g_persist = 0;
   }
   return g_persist;
@@ -154,7 +153,6 @@ static int gemm_planes_impl(const mt_gemm_planes_desc* d, void* stream) {
   const bool cpl = d->c_planes != nullptr;
   if (!d->C && !cpl) return fail(MT_ERR_ARG, "mt_gemm_planes: no output");
   if (cpl && epi != MT_EPI_GEGLU && epi != MT_EPI_GEGLU_BWD) return fail(MT_ERR_UNSUPPORTED, "mt_gemm_planes: plane output only from the GEGLU pair");
-  if (!cpl && !d->C) return fail(MT_ERR_ARG, "mt_gemm_planes: C is null");
   if (epi == MT_EPI_BIAS_RES && !d->R) return fail(MT_ERR_ARG, "mt_gemm_planes: BIAS_RES needs R");
   if (epi == MT_EPI_GEGLU && (d->n_half * 2 != d->N || (d->n_half & 63))) return fail(MT_ERR_ARG, "mt_gemm_planes GEGLU: N must be 2*n_half, n_half %% 64 == 0");
   if (epi == MT_EPI_GEGLU_BWD && (!d->C2 || d->n_half != d->N || (d->n_half & 31)))
@@ -189,49 +187,30 @@ static int gemm_planes_impl(const mt_gemm_planes_desc* d, void* stream) {
     a.c_planes = d->c_planes; a.c_pstride = mt_planes_elems(d->M, c_cols); a.ldcp = (c_cols + 15) >> 4;
   }
 
-  const int m_tiles = (d->M + 127) / 128, n_tiles = (d->N + 127) / 128;
-  dim3 grid(m_tiles * n_tiles, 1, 1);
+  // one column group's panels: the bf16 planes of B the loop reads
+  const TileGrid tg = tile_grid(d->M, d->N, 128, 128, (int64_t)128 * d->K * 2 * np);
+  const int m_tiles = tg.m_tiles, n_tiles = tg.n_tiles;
   if (op == MT_OP_TN) {
     if (epi != MT_EPI_ATOMIC) return fail(MT_ERR_UNSUPPORTED, "mt_gemm_planes TN: ATOMIC epilogue only (C pre-zeroed)");
-    // K-range-major split-K (gemm_split.hpp): a multiple of 8 ranges, m_tiles * n_tiles blocks per range
-    int splits = d->split_k;
-    if (splits <= 0) {
-      static const int target = getenv("MT_WGRAD_BLOCKS") ? atoi(getenv("MT_WGRAD_BLOCKS")) : 640;
-      splits = (target + (int)grid.x - 1) / (int)grid.x;
-      const int max_splits = d->K / 256 > 0 ? d->K / 256 : 1;
-      if (splits > max_splits) splits = max_splits;
-    }
-    splits = (splits + 4) / 8 * 8;
-    if (splits < 8) splits = 8;
-    int chunk = (d->K + splits - 1) / splits;
-    chunk = (chunk + 15) / 16 * 16;
-    a.k_chunk = chunk; a.xcd_k = 1;
-    grid.y = (unsigned)(((d->K + chunk - 1) / chunk + 7) / 8 * 8);
-    if (int rc = det_gemm_setup(a.C, a.ldc, a.det_slab, d->M, d->N, (d->K + chunk - 1) / chunk, false, s)) return rc;
-    return launch(0, a, grid);
+    // always K-range-major (gemm_split.hpp), also for the caller's own split_k: m_tiles * n_tiles blocks per range, plain tile order
+    static const int target = env_int("MT_WGRAD_BLOCKS", 640);
+    const SplitK sk = split_k_ranges(d->K, m_tiles * n_tiles, d->split_k, target, 16, K_XCD);
+    a.k_chunk = sk.k_chunk; a.xcd_k = sk.xcd_k;
+    if (int rc = det_gemm_setup(a.C, a.ldc, a.det_slab, d->M, d->N, sk.ranges, false, s)) return rc;
+    return launch(0, a, dim3(m_tiles * n_tiles, sk.grid_y, 1));
   }
-  {
-    // forward / data-gradient GEMMs sit on the critical queue, the weight gradients they share the matrix cores with do not
-    static const int prio = getenv("MT_PLANES_MAIN_PRIO") ? atoi(getenv("MT_PLANES_MAIN_PRIO")) : 0;
-    a.wave_prio = prio;
-  }
-  if (m_tiles >= 32 && n_tiles >= 2 && !getenv("MT_NO_L2_BLOCKING")) {
-    const int64_t panel = (int64_t)128 * d->K * 2 * np;   // one column group's B panels: the bf16 planes the loop reads
-    static const int64_t group_bytes = getenv("MT_PLANES_GROUP_KB") ? (int64_t)atoi(getenv("MT_PLANES_GROUP_KB")) << 10 : (2 << 20);
-    int gn = (int)(group_bytes / (panel > 0 ? panel : 1));
-    if (gn < 1) gn = 1;
-    if (gn > n_tiles) gn = n_tiles;
-    a.group_n = gn;
-    grid.x = 8 * ((m_tiles + 7) / 8) * n_tiles;
-  }
+  dim3 grid(tg.grid_x, 1, 1);
+  a.group_n = tg.group_n;
+  // forward / data-gradient GEMMs sit on the critical queue, the weight gradients they share the matrix cores with do not
+  static const int prio = env_int("MT_PLANES_MAIN_PRIO", 0);
+  a.wave_prio = prio;
   // stream-K over a persistent grid (gemm_planes.hpp) when the caller lends a workspace: two resident blocks per CU share the
-  // linearised (tile, k-step) list evenly.  Tiny problems (less than ~4 k-steps per block) keep one block per tile.
-  const int sk_env = 1;   // (the caller decides by lending a workspace; measured slower than one block per tile on the TimeSformer's shapes: the loop is power-bound and a tile tail's idle CUs give their power to the busy ones)
+  // linearised (tile, k-step) list evenly.  Tiny problems (less than ~4 k-steps per block) keep one block per tile.  (Measured
+  // slower than one block per tile on the TimeSformer's shapes: the loop is power-bound and a tile tail's idle CUs give their
+  // power to the busy ones.)
   bool sk = false;
-  if (sk_env && d->sk_workspace && d->sk_workspace_bytes >= mt_gemm_planes_workspace_bytes() && !((uintptr_t)d->sk_workspace & 255)) {
-    static const int per_cu = getenv("MT_PLANES_SK_BLOCKS") ? atoi(getenv("MT_PLANES_SK_BLOCKS")) : 2;
-    int g = cu_count() * per_cu;
-    g = g / 8 * 8;
+  if (d->sk_workspace && d->sk_workspace_bytes >= mt_gemm_planes_workspace_bytes() && !((uintptr_t)d->sk_workspace & 255)) {
+    int g = cu_count() * 2 / 8 * 8;
     if (g > kSkMaxGrid) g = kSkMaxGrid;
     const int64_t units = (int64_t)m_tiles * n_tiles * (((d->K + 15) / 16 + 1) / 2);     // pairs of k-steps
     if (g >= 8 && units >= (int64_t)g * 2 && units < (1ll << 30)) {

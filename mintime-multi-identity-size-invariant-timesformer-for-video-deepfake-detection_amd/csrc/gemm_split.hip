@@ -12,10 +12,7 @@ namespace {
 // 0 = fp32 MFMA everywhere, 1 = split-operand bf16x6 where eligible.  Process-wide; MT_GEMM_SPLIT sets the initial value.
 int g_mode = -1;
 int mode() {
-  if (g_mode < 0) {
-    const char* e = getenv("MT_GEMM_SPLIT");
-    g_mode = e ? (atoi(e) != 0) : 1;
-  }
+  if (g_mode < 0) g_mode = env_int("MT_GEMM_SPLIT", 1) != 0;
   return g_mode;
 }
 
@@ -95,15 +92,6 @@ namespace mt {
 // Returns 1 when the problem is not eligible (caller falls back), 0 on success, < 0 on error.
 int try_launch_split(const mt_gemm_desc* d, GemmArgs a, hipStream_t s) {
   if (!mode()) return 1;
-  if (const char* f = getenv("MT_SPLIT_ONLY_EPI")) {                // bisection aid: only this epilogue (and K, if given) takes the split loop
-    if (d->epilogue != atoi(f)) return 1;
-    if (const char* k = getenv("MT_SPLIT_ONLY_K")) if (d->K != atoi(k)) return 1;
-    static int calls = 0;                                           // ... and only calls [MT_SPLIT_FIRST, MT_SPLIT_LAST] of those
-    const int idx = calls++;
-    if (const char* lo = getenv("MT_SPLIT_FIRST")) if (idx < atoi(lo)) return 1;
-    if (const char* hi = getenv("MT_SPLIT_LAST")) if (idx > atoi(hi)) return 1;
-    if (getenv("MT_SPLIT_TRACE")) fprintf(stderr, "[split] call %d: op %d M %d N %d K %d\n", idx, d->op, d->M, d->N, d->K);
-  }
   if (matmul_precision() == MT_PRECISION_HIGH) return launch_split_high(d, a, s);
   return split_dispatch::launch_split_tier<true>(d, a, s);
 }

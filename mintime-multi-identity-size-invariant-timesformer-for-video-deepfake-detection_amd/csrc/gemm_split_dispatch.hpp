@@ -6,17 +6,17 @@
 #include "../../include/mintime_hip.h"
 #include "common.hpp"
 #include "gemm_split.hpp"
+#include "gemm_geometry.hpp"
 #include "det.hpp"
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 namespace mt {
 namespace split_dispatch {
 
-enum { S_BIG = 0, S_MID = 1, S_SMALL = 2, S_COUNT };      // 128 x 128 (4 waves of 64 x 64), 128 x 64 (64 x 32), 64 x 64 (32 x 32)
+enum { S_BIG = 0, S_MID = 1, S_COUNT };      // 128 x 128 (4 waves of 64 x 64), 128 x 64 (64 x 32)
 struct Var { int bm, bn; };
-constexpr Var kVar[S_COUNT] = {{128, 128}, {128, 64}, {64, 64}};
+constexpr Var kVar[S_COUNT] = {{128, 128}, {128, 64}};
 
 template <bool X6, int WM, int WN, int TM, int TN, int AL, int BL, int EPI, int MINW, bool BAL, int PRO = PRO_NONE, bool BPL = false>
 int launch_one(const GemmArgs& a, dim3 grid, hipStream_t s) {
@@ -25,12 +25,6 @@ int launch_one(const GemmArgs& a, dim3 grid, hipStream_t s) {
   size_t lds = BPL ? (size_t)(6 * BM + 9 * BN) * 32 : (size_t)2 * (X6 ? 3 : 2) * (BM + BN) * 32;      // two stages of three (two) planes per operand
   if (PRO == PRO_BN_SWISH_GATE) lds += (size_t)(2 + (BM - 1) / a.hw + 2) * a.K * 4;      // scale, shift, gate rows of the images a row tile touches
   if (PRO == PRO_BN_BWD && AL == LAYOUT_KCONTIG) lds += (size_t)3 * a.K * 4;             // ka, kb, kc
-  if (!BAL && AL == LAYOUT_KMAJOR) {
-    // experiment knob: extra LDS per weight-gradient block (8192 -> two instead of three blocks per CU, leaving room for a
-    // main-stream GEMM block).  Measured in-step: 55.3 vs 54.4 ms -- the weight gradients lose more than the main stream gains.
-    static const int pad = getenv("MT_WGRAD_LDS_PAD") ? atoi(getenv("MT_WGRAD_LDS_PAD")) : 0;
-    lds += (size_t)pad;
-  }
   if (lds > 160 * 1024) return 1;      // not this way: the caller falls back to the fp32 kernels
   {
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds);
@@ -45,37 +39,32 @@ int launch_variant(int v, const GemmArgs& a, dim3 grid, hipStream_t s) {
   // Balanced accumulators (gemm_split.hpp: BAL) wherever a result feeds further contractions (activations, data gradients): the
   // bf16 pipe's rounding bias is only a problem when it adds up coherently through depth.  Weight gradients (TN) are leaves --
   // their error goes no further than lr x bias into the next step's weights -- and take the single-accumulator loop
-  // (max / rms error equal to the fp32 pipe's, 6-8 % faster, 146 instead of 206 VGPRs).  MT_SPLIT_WGRAD_BAL=1 balances them too.
+  // (max / rms error equal to the fp32 pipe's, 6-8 % faster, 146 instead of 206 VGPRs).
   if constexpr (AL == LAYOUT_KMAJOR && BL == LAYOUT_KMAJOR) {
-    static const bool wbal = getenv("MT_SPLIT_WGRAD_BAL") && atoi(getenv("MT_SPLIT_WGRAD_BAL")) != 0;
-    if (!wbal) {
-      if (v == S_BIG) return launch_one<X6, 2, 2, 2, 2, AL, BL, EPI, 2, false, PRO>(a, grid, s);
-      if (v == S_MID) return launch_one<X6, 2, 2, 2, 1, AL, BL, EPI, 3, false, PRO>(a, grid, s);
-      if (v == S_SMALL) return launch_one<X6, 2, 2, 1, 1, AL, BL, EPI, 4, false, PRO>(a, grid, s);
+    return v == S_BIG ? launch_one<X6, 2, 2, 2, 2, AL, BL, EPI, 2, false, PRO>(a, grid, s)
+                      : launch_one<X6, 2, 2, 2, 1, AL, BL, EPI, 3, false, PRO>(a, grid, s);
+  } else {
+    // (the B-planes variant is a six-product loop: at tier high the call goes on to the normal instance)
+    if constexpr (X6 && AL == LAYOUT_KCONTIG && BL == LAYOUT_KCONTIG && EPI != EPI_STATS && PRO == PRO_NONE) {
+      // weight pre-split into bf16 planes (mt_split_planes): B by DMA, 128 x 128 tiles only.  Bit-identical to the in-kernel split.
+      // Round 2: 7-12 % slower (hipcc's vmcnt for the staged A tile also drained the DMA of the same step).  Round 3: the A loads
+      // are inline asm under one counted wait per step (no compiler-inserted vmcnt left in the loop, checked in the ISA) -- and the
+      // variant now runs EQUAL to the in-kernel split, not faster (profiles/r03_split_planes_manual_waits.txt:
+      // QKV 154.7 / 153.6 us, FF2 203.8 / 201.2, FF1 data gradient 353.5 / 352.0, 4096^3 747 / 780), with two or with three A
+      // register sets in flight: the loop is limited by its matrix + LDS issue, not by operand delivery.  Stays opt-in
+      // (MT_SPLIT_PLANES=1; read per call: tests toggle it).
+      const bool planes_on = env_int("MT_SPLIT_PLANES", 0) != 0;
+      if (planes_on && a.b_planes && (a.K % 16) == 0 && a.k_chunk == 0 && (a.ldb % 8) == 0 && a.b_map.gin == 0 && (v == S_BIG || EPI == EPI_GEGLU_BWD))
+        return launch_one<X6, 2, 2, 2, 2, AL, BL, EPI, 2, true, PRO_NONE, true>(a, grid, s);
     }
+    if constexpr (EPI != EPI_GEGLU) {      // (GEGLU needs the 128-column tile: launch_split_tier gives it S_BIG)
+      if (v == S_MID) return launch_one<X6, 2, 2, 2, 1, AL, BL, EPI, 3, true, PRO>(a, grid, s);
+    }
+    return launch_one<X6, 2, 2, 2, 2, AL, BL, EPI, 2, true, PRO>(a, grid, s);
   }
-  // (the B-planes variant is a six-product loop: at tier high the call goes on to the normal instance)
-  if constexpr (X6 && AL == LAYOUT_KCONTIG && BL == LAYOUT_KCONTIG && EPI != EPI_STATS && PRO == PRO_NONE) {
-    // weight pre-split into bf16 planes (mt_split_planes): B by DMA, 128 x 128 tiles only.  Bit-identical to the in-kernel split.
-    // Round 2: 7-12 % slower (hipcc's vmcnt for the staged A tile also drained the DMA of the same step).  Round 3: the A loads are
-    // inline asm under one counted wait per step (no compiler-inserted vmcnt left in the loop, checked in the ISA) -- and the variant
-    // now runs EQUAL to the in-kernel split, not faster (profiles/r03_split_planes_manual_waits.txt:
-    // QKV 154.7 / 153.6 us, FF2 203.8 / 201.2, FF1 data gradient 353.5 / 352.0, 4096^3 747 / 780), with two or with three A register
-    // sets in flight: the loop is limited by its matrix + LDS issue, not by operand delivery.  Stays opt-in (MT_SPLIT_PLANES=1).
-    const bool planes_on = getenv("MT_SPLIT_PLANES") && atoi(getenv("MT_SPLIT_PLANES")) != 0;
-    if (planes_on && a.b_planes && (a.K % 16) == 0 && a.k_chunk == 0 && (a.ldb % 8) == 0 && a.b_map.gin == 0 && (v == S_BIG || EPI == EPI_GEGLU_BWD))
-      return launch_one<X6, 2, 2, 2, 2, AL, BL, EPI, 2, true, PRO_NONE, true>(a, grid, s);
-  }
-  if (v == S_BIG) return launch_one<X6, 2, 2, 2, 2, AL, BL, EPI, 2, true, PRO>(a, grid, s);
-  if constexpr (EPI != EPI_GEGLU) {
-    if (v == S_MID) return launch_one<X6, 2, 2, 2, 1, AL, BL, EPI, 3, true, PRO>(a, grid, s);
-    if (v == S_SMALL) return launch_one<X6, 2, 2, 1, 1, AL, BL, EPI, 4, true, PRO>(a, grid, s);
-  }
-  return fail(MT_ERR_UNSUPPORTED, "mt_gemm(split): no instance for variant %d", v);
 }
 
-
-// The body of try_launch_split() behind its mode check and its bisection filter.  Returns 1 when the problem is not eligible (caller falls back), 0 on
+// The body of try_launch_split() behind its mode check.  Returns 1 when the problem is not eligible (caller falls back), 0 on
 // success, < 0 on error.
 template <bool X6>
 int launch_split_tier(const mt_gemm_desc* d, GemmArgs a, hipStream_t s) {
@@ -83,24 +72,14 @@ int launch_split_tier(const mt_gemm_desc* d, GemmArgs a, hipStream_t s) {
   if (d->K % 8 || d->M < 128 || d->N < 64) return 1;     // K % 16 == 8: the last k-tile is half zeros (gemm_split.hpp k_tail)
   if (d->prologue == MT_PRO_BN_SWISH_GATE) {
     // MBConv project convolution (forward): the operand transform rides in the staging registers (gemm_split.hpp PRO)
-    static const int pro_on = getenv("MT_SPLIT_PRO") ? atoi(getenv("MT_SPLIT_PRO")) : 1;
-    if (!pro_on || d->op != MT_OP_NT || d->M < 4096 || d->K < 256 || (d->K % 16)) return 1;
+    if (d->op != MT_OP_NT || d->M < 4096 || d->K < 256 || (d->K % 16)) return 1;
     if (d->epilogue != MT_EPI_STATS && d->epilogue != MT_EPI_STORE) return 1;
     // tile width by padding waste: 128 columns unless 64-wide tiles waste fewer padded columns
     const int pad128 = (d->N + 127) / 128 * 128, pad64 = (d->N + 63) / 64 * 64;
     const int v = pad64 < pad128 ? S_MID : S_BIG;
-    const Var var = kVar[v];
-    const int m_tiles = (d->M + var.bm - 1) / var.bm, n_tiles = (d->N + var.bn - 1) / var.bn;
-    dim3 grid(m_tiles * n_tiles, 1, 1);
-    a.group_n = 0; a.k_chunk = 0; a.trace = nullptr;
-    if (m_tiles >= 32 && n_tiles >= 2 && !getenv("MT_NO_L2_BLOCKING")) {
-      const int64_t panel = (int64_t)var.bn * d->K * 4;
-      int gn = (int)((2 << 20) / (panel > 0 ? panel : 1));
-      if (gn < 1) gn = 1;
-      if (gn > n_tiles) gn = n_tiles;
-      a.group_n = gn;
-      grid.x = 8 * ((m_tiles + 7) / 8) * n_tiles;
-    }
+    const TileGrid tg = tile_grid(d->M, d->N, kVar[v].bm, kVar[v].bn, (int64_t)kVar[v].bn * d->K * 4);
+    dim3 grid(tg.grid_x, 1, 1);
+    a.group_n = tg.group_n; a.k_chunk = 0; a.trace = nullptr;
     constexpr int KC = LAYOUT_KCONTIG;
     if (d->epilogue == MT_EPI_STATS)
       return v == S_BIG ? launch_one<X6, 2, 2, 2, 2, KC, KC, EPI_STATS, 2, true, PRO_BN_SWISH_GATE>(a, grid, s)
@@ -113,7 +92,7 @@ int launch_split_tier(const mt_gemm_desc* d, GemmArgs a, hipStream_t s) {
   // expand convolutions from stage 5 on and its head; the weight gradients' K is the row count).
   const bool bn_bwd = d->prologue == MT_PRO_BN_BWD;
   if (bn_bwd) {
-    static const int on = getenv("MT_SPLIT_BN_BWD") ? atoi(getenv("MT_SPLIT_BN_BWD")) : 1;
+    static const int on = env_int("MT_SPLIT_BN_BWD", 1);
     if (!on || d->a_map.gin != 0) return 1;
     const bool nn = d->op == MT_OP_NN && (d->epilogue == MT_EPI_STORE || d->epilogue == MT_EPI_BIAS_RES);
     const bool tn = d->op == MT_OP_TN && d->epilogue == MT_EPI_ATOMIC;
@@ -121,74 +100,38 @@ int launch_split_tier(const mt_gemm_desc* d, GemmArgs a, hipStream_t s) {
   } else if (d->prologue != MT_PRO_NONE) return 1;
   // short contractions stay on the fp32 pipe: the matrix time they could save is small next to their epilogue, and the bf16 pipe's
   // residual rounding bias (gemm_split.hpp) is then kept out of the extractors' long chains of small-K convolutions
-  static const int min_k = getenv("MT_SPLIT_MIN_K") ? atoi(getenv("MT_SPLIT_MIN_K")) : 512;
+  static const int min_k = env_int("MT_SPLIT_MIN_K", 512);
   if (d->K < min_k) return 1;
   if (d->epilogue == MT_EPI_STATS && d->M < 4096) return 1;
   if (d->epilogue == MT_EPI_GEGLU && (d->n_half & 63)) return 1;
   // a handful of tiles: the fp32 kernels' small tiles fill the chip better -- unless it is a weight gradient over very many rows,
   // whose K-ranges supply the blocks
   if ((int64_t)d->M * d->N < (1 << 18) && !(d->op == MT_OP_TN && d->K >= 8192 && (int64_t)d->M * d->N >= (1 << 15))) return 1;
-  int v = S_BIG;
-  if (d->epilogue == MT_EPI_GEGLU_BWD) v = S_MID;
-  else if (d->N < 128) v = S_MID;
-  if (const char* f = getenv("MT_SPLIT_VARIANT")) v = atoi(f);      // tuning experiments only
-  if (const char* f = getenv("MT_SPLIT_VARIANT_EPI")) {             // "epi:variant[,epi:variant...]"
-    for (const char* q = f; q && *q; q = strchr(q, ',') ? strchr(q, ',') + 1 : nullptr) {
-      int e = -1, vv = -1;
-      if (sscanf(q, "%d:%d", &e, &vv) == 2 && e == d->epilogue + 10 * d->op) v = vv;
-    }
-  }
-  if (v != S_BIG && d->epilogue == MT_EPI_GEGLU) v = S_BIG;
-  if (v < 0 || v >= S_COUNT) return 1;
-  const Var var = kVar[v];
-  const int m_tiles = (d->M + var.bm - 1) / var.bm, n_tiles = (d->N + var.bn - 1) / var.bn;
-  dim3 grid(m_tiles * n_tiles, 1, 1);
-  a.group_n = 0;
+  // 128 x 128 tiles; 128 x 64 for the GEGLU-backward epilogue and for narrow outputs
+  const int v = d->epilogue == MT_EPI_GEGLU_BWD || d->N < 128 ? S_MID : S_BIG;
+  const TileGrid tg = tile_grid(d->M, d->N, kVar[v].bm, kVar[v].bn, (int64_t)kVar[v].bn * d->K * 4);
+  dim3 grid(tg.grid_x, 1, 1);
+  a.group_n = tg.group_n;
   a.k_chunk = 0;
   a.trace = nullptr;
-  if (m_tiles >= 32 && n_tiles >= 2 && !getenv("MT_NO_L2_BLOCKING")) {
-    const int64_t panel = (int64_t)var.bn * d->K * 4;
-    int gn = (int)((2 << 20) / (panel > 0 ? panel : 1));
-    if (gn < 1) gn = 1;
-    if (gn > n_tiles) gn = n_tiles;
-    a.group_n = gn;
-    grid.x = 8 * ((m_tiles + 7) / 8) * n_tiles;
-  }
   if (d->op == MT_OP_TN || d->epilogue == MT_EPI_ATOMIC) {
-    int splits = d->split_k;
-    if (d->op == MT_OP_TN && splits <= 0) {
-      const int tiles = m_tiles * n_tiles;
-      // blocks per launch.  Round 2: 2048 (16-49 K-ranges, whose fp32-atomic partial sums were as much HBM-side traffic as the
-      // operands).  With the K-range-major XCD mapping the step time is flat from 384 to 2048 (53.7-54.2 ms); 640 keeps 8-40
-      // ranges: partial-sum traffic 104 -> ~48 MB per launch (family total ~1.45x the algorithmic bytes).
-      static const int target = getenv("MT_WGRAD_BLOCKS") ? atoi(getenv("MT_WGRAD_BLOCKS")) : 640;   // tuning knob
-      splits = (target + tiles - 1) / tiles;
-      const int max_splits = d->K / 256 > 0 ? d->K / 256 : 1;
-      if (splits > max_splits) splits = max_splits;
-    }
-    if (splits < 1) splits = 1;
-    static const int xcd_k_on = getenv("MT_WGRAD_XCD_K") ? atoi(getenv("MT_WGRAD_XCD_K")) : 1;
-    if (d->op == MT_OP_TN && xcd_k_on && d->split_k <= 0 && d->K >= 8 * 256 && d->a_map.gin == 0 && d->b_map.gin == 0) {
-      // K-range-major over the XCDs (gemm_split.hpp): a multiple of 8 ranges, exactly m_tiles * n_tiles blocks per range
-      const int max_splits8 = (d->K / 256) / 8 * 8;                    // (>= 8: K >= 8 * 256 here)
-      splits = (splits + 4) / 8 * 8;
-      if (splits > max_splits8) splits = max_splits8;
-      if (splits < 8) splits = 8;
-      int chunk = (d->K + splits - 1) / splits;
-      chunk = (chunk + 15) / 16 * 16;
-      a.k_chunk = chunk;
-      a.xcd_k = 1;
+    // blocks per weight-gradient launch.  Round 2: 2048 (16-49 K-ranges, whose fp32-atomic partial sums were as much HBM-side
+    // traffic as the operands).  With the K-range-major XCD mapping the step time is flat from 384 to 2048 (53.7-54.2 ms); 640
+    // keeps 8-40 ranges: partial-sum traffic 104 -> ~48 MB per launch (family total ~1.45x the algorithmic bytes).
+    static const int target = env_int("MT_WGRAD_BLOCKS", 640);   // tuning knob
+    static const int xcd_k_on = env_int("MT_WGRAD_XCD_K", 1);
+    const bool tn = d->op == MT_OP_TN;
+    const bool xcd_k = tn && xcd_k_on && d->split_k <= 0 && d->K >= 8 * 256 && d->a_map.gin == 0 && d->b_map.gin == 0;
+    const SplitK sk = split_k_ranges(d->K, tg.m_tiles * tg.n_tiles, d->split_k, tn ? target : 0, 16, xcd_k ? K_XCD_CAPPED : K_PLAIN);
+    a.k_chunk = sk.k_chunk;
+    a.xcd_k = sk.xcd_k;
+    grid.y = sk.grid_y;
+    if (xcd_k) {       // one block per tile and range
       a.group_n = 0;
-      grid.x = m_tiles * n_tiles;
-      grid.y = ((d->K + chunk - 1) / chunk + 7) / 8 * 8;               // no K-range beyond the last non-empty group of 8
-    } else {
-      int chunk = (d->K + splits - 1) / splits;
-      chunk = (chunk + 15) / 16 * 16;
-      a.k_chunk = chunk;
-      grid.y = (d->K + chunk - 1) / chunk;
+      grid.x = tg.m_tiles * tg.n_tiles;
     }
     if (d->epilogue == MT_EPI_ATOMIC)
-      if (int rc = det_gemm_setup(a.C, a.ldc, a.det_slab, d->M, d->N, (d->K + a.k_chunk - 1) / a.k_chunk, a.c_map.gin != 0, s)) return rc;
+      if (int rc = det_gemm_setup(a.C, a.ldc, a.det_slab, d->M, d->N, sk.ranges, a.c_map.gin != 0, s)) return rc;
   }
 
   if (bn_bwd) {

@@ -1537,7 +1537,7 @@ extern "C" int mt_layernorm_bwd(const float* dy, const float* x, const float* st
   if (dim <= 0 || (dim & 3) || dim > 1024) return fail(MT_ERR_ARG, "mt_layernorm_bwd: dim %d unsupported", dim);
   if (rows <= 0) return 0;
   int blocks = (rows + 3) / 4;
-  static const int cap = getenv("MT_LN_BWD_BLOCKS") ? atoi(getenv("MT_LN_BWD_BLOCKS")) : 256;     // tuning knob
+  static const int cap = env_int("MT_LN_BWD_BLOCKS", 256);     // tuning knob
   if (blocks > cap) blocks = cap;
   DetScope det((hipStream_t)stream, 3, blocks, dim, true, true);     // deterministic mode: the three column sums by block order
   if (dim <= 512)
@@ -1564,7 +1564,7 @@ extern "C" int mt_layernorm_bwd_rows(const float* dy, const float* x, const floa
   const int rp = (rows + 31) & ~31;
   const PlaneRef dxp{reinterpret_cast<__bf16*>(dx_planes), (int64_t)rp * dim, dim >> 4, rp};
   const int blocks = ln_rows_blocks(rows);
-  static const int keep = getenv("MT_LN_ROWS_KEEP") ? atoi(getenv("MT_LN_ROWS_KEEP")) : 1;
+  static const int keep = env_int("MT_LN_ROWS_KEEP", 1);
   if (dim <= 512 && keep)
     hipLaunchKernelGGL(layernorm_bwd_rows_kernel2k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, x, stats, gamma, dx, dx_in, rows, dim, dxp);
   else if (dim <= 512)
@@ -1576,7 +1576,7 @@ extern "C" int mt_layernorm_bwd_rows(const float* dy, const float* x, const floa
 
 static int ln_rows_blocks(int rows) {
   int blocks = (rows + 3) / 4;
-  static const int cap = getenv("MT_LN_ROWS_BLOCKS") ? atoi(getenv("MT_LN_ROWS_BLOCKS")) : 1024;    // tuning knob
+  static const int cap = env_int("MT_LN_ROWS_BLOCKS", 1024);    // tuning knob
   if (blocks > cap) blocks = cap;
   return blocks < 1 ? 1 : blocks;
 }
@@ -1660,7 +1660,7 @@ extern "C" int mt_embed_bwd(const float* dx, float* dcls, float* dpos_emb, float
   const int N = 1 + F * n;
   if (det_enabled()) {
     hipStream_t s = (hipStream_t)stream;
-    static const bool walk = getenv("MT_DET_EMBED_WALK") != nullptr;        // A/B aid: round 4's run walk for all three gradients
+    static const bool walk = env_set("MT_DET_EMBED_WALK");        // A/B aid: round 4's run walk for all three gradients
     const int srows = dsize_emb ? size_rows : 1;
     // cls token: B ordered adds per column (kind 0 of the walk kernel); the tables: integer-limb scatter + decode
     hipLaunchKernelGGL(embed_bwd_det_kernel, dim3((dim + 63) / 64, walk ? 3 : 1), dim3(64), 0, s, dx, dcls,
@@ -1685,7 +1685,7 @@ extern "C" int mt_embed_bwd(const float* dx, float* dcls, float* dpos_emb, float
     }
     return 0;
   }
-  static const bool rows_form = getenv("MT_EMBED_BWD_ROWS") != nullptr;        // A/B aid: the row-per-wavefront kernel
+  static const bool rows_form = env_set("MT_EMBED_BWD_ROWS");        // A/B aid: the row-per-wavefront kernel
   if (rows_form || F * n + 1 != N)
     hipLaunchKernelGGL(embed_bwd_kernel, dim3((B * N + 3) / 4), dim3(256), 0, (hipStream_t)stream, dx, dcls, dpos_emb, dsize_emb,
                        positions, sizes, B, N, n, F, dim, pos_rows, dsize_emb ? size_rows : 1);
@@ -1705,9 +1705,9 @@ extern "C" int mt_attn_bwd(const float* qkv, const float* dout, float* dqkv, con
   const int N = 1 + F * n;
   const int rp = (B * N + 31) & ~31, ld = 3 * H * DH;
   const PlaneRef dp{reinterpret_cast<__bf16*>(dqkv_planes), (int64_t)rp * ld, ld / 16, rp};
-  static const bool time_old = getenv("MT_ATTN_TIME_OLD") != nullptr;    // A/B aid: the 7-patches-per-wavefront kernel
-  static const bool valu = getenv("MT_ATTN_VALU") != nullptr;            // A/B aid: the one-lane-per-query space kernel
-  static const bool fact_on = !getenv("MT_ATTN_CLS_FACT") || atoi(getenv("MT_ATTN_CLS_FACT")) != 0;
+  static const bool time_old = env_set("MT_ATTN_TIME_OLD");    // A/B aid: the 7-patches-per-wavefront kernel
+  static const bool valu = env_set("MT_ATTN_VALU");            // A/B aid: the one-lane-per-query space kernel
+  static const bool fact_on = env_int("MT_ATTN_CLS_FACT", 1) != 0;
   // with plane output the fp32 dqkv is working memory: the cls query's contribution to the patch keys crosses to the patch kernel as two
   // scalars per key and head (kernels that understand it: the MFMA space kernel, the one-patch-per-wavefront time kernel)
   const bool fact = fact_on && dqkv_planes && ((mode == 1 && !valu) || (mode == 0 && !time_old && (F == 8 || F == 16)));
@@ -1722,7 +1722,7 @@ extern "C" int mt_attn_bwd(const float* qkv, const float* dout, float* dqkv, con
     if (valu) rc = launch_patch_bwd<1, 50, 1, 64, 2>(qkv, dout, dqkv, mask, ident, B, H, F, n, scale, dp, det.log, s);
     else {
       const int64_t waves = (int64_t)B * H * F;
-      static const bool xp = !(getenv("MT_ATTN_SPACE_XP") && atoi(getenv("MT_ATTN_SPACE_XP")) == 0);    // 0: phase B recomputes P / dS (round 5)
+      static const bool xp = env_int("MT_ATTN_SPACE_XP", 1) != 0;    // 0: phase B recomputes P / dS (round 5)
       const dim3 grid((unsigned)((waves + 3) / 4));
       if (xp) {
         constexpr size_t lds = (size_t)4 * 2 * 64 * XP_LD * sizeof(float);

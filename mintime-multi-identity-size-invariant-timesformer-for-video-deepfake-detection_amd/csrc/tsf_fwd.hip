@@ -699,13 +699,13 @@ extern "C" int mt_attn_fwd(const float* qkv, float* out, float* cls_att, const u
   int rc = check_launch("mt_attn_fwd(cls)");
   if (rc || mode == 2) return rc;                 // mode 2: the cls query only (out row 0 of every clip; the patch rows are not written)
   if (mode == 1) {
-    static const bool valu = getenv("MT_ATTN_VALU") != nullptr;     // A/B aid: the one-lane-per-query kernel
+    static const bool valu = env_set("MT_ATTN_VALU");     // A/B aid: the one-lane-per-query kernel
     if (valu) return launch_patch<1, 50, 1, 64, 2>(qkv, out, mask, ident, B, H, F, n, scale, op, s);
     const int64_t waves = (int64_t)B * H * F;
     hipLaunchKernelGGL(attn_space_fwd_mfma_kernel<4>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, qkv, out, B, H, F, n, scale, op);
     return check_launch("mt_attn_fwd(space, mfma)");
   }
-  static const bool time_old = getenv("MT_ATTN_TIME_OLD") != nullptr;    // A/B aid: the 7-patches-per-wavefront kernel
+  static const bool time_old = env_set("MT_ATTN_TIME_OLD");    // A/B aid: the 7-patches-per-wavefront kernel
   if (!time_old) {
     switch (F) {
       case 8: return launch_time_fwd<8, 4>(qkv, out, mask, ident, B, H, n, scale, op, s);
