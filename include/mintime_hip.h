@@ -613,6 +613,17 @@ int mt_baseline_head_bwd(const float* dlogits, const float* pooled, const float*
  *   for j < Tsplit, else out2 [B][Tout - Tsplit][H][W][4]; v = (u / 255 - 0.45) / 0.225 (normalize) or u; src uint8 (is_u8) or fp32
  *   with element strides (b, f, h, w, c).  Both pathways in one launch: reference utils.py:166-186 (UniformTemporalSubsample, /255,
  *   Normalize, PackPathway).
+ * mt_sf_ingest_bwd: the ingest's adjoint, dsrc[b][f][h][w][c] = k * sum over the output frames j with fidx[j] == f of
+ *   dout_j[b][.][h][w][c], c < 3 (dout_j in dout [B][Tsplit][H][W][4] for j < Tsplit, else in dout2; the 4th channel is not read);
+ *   k = 1 / (255 * 0.225) (normalize) or 1.  The inverse map comes CSR style: start (int32 [F + 1]) and jlist (int32 [Tout], j
+ *   ascending inside a frame): frame f sums jlist[start[f] .. start[f+1]) in that order, a frame nobody selected gets exact 0.
+ *   dsrc is fp32 with the element strides (b, f, h, w, c) of mt_sf_ingest's src; written, one writer per element.
+ * mt_sf_stem_dgrad: the stems' data gradient down to the clip (csrc/sf_stem_dgrad.hip), with Ho = (H-1)/2 + 1, Wo = (W-1)/2 + 1:
+ *   dx[n][t][h][w][c] = sum_{dt,kh,kw,co} dz[n][t + kt/2 - dt][(h+3-kh)/2][(w+3-kw)/2][co] * w[co][c][dt][kh][kw] over the taps with
+ *   even h+3-kh and w+3-kw and a dz index on the grid.  dz [N][T][Ho][Wo] rows of K floats, pitch ldz (% 4 == 0), 16-byte aligned;
+ *   wt = the weight repacked by the host to [kt*K][160]: row dt*K + co, column (kh*7 + kw)*3 + c, columns 147..159 zero;
+ *   dx [N][T][H][W][4], 16-byte aligned, written (4th channel 0).  (kt, K) = (1, 64) (slow stem) or (5, 8) (fast stem), any N, T, H,
+ *   W >= 1; anything else returns MT_ERR_UNSUPPORTED before a launch.  A gather on v_mfma_f32_32x32x2_f32: no atomics.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct {
   int N, T, H, W, C;                      /* input grid and channels */
@@ -646,6 +657,9 @@ int mt_sf_head_dfeat(const float* dpool, float* dfeat, int64_t ldf, int B, int T
                      int CT, void* stream);
 int mt_sf_ingest(const void* src, int is_u8, int64_t sb, int64_t sf, int64_t sh, int64_t sw, int64_t sc, const int* fidx, int Tout,
                  int Tsplit, int B, int H, int W, int normalize, float* out, float* out2, void* stream);
+int mt_sf_ingest_bwd(const float* dout, const float* dout2, const int* start, const int* jlist, int F, int Tout, int Tsplit, int B, int H,
+                     int W, int normalize, float* dsrc, int64_t sb, int64_t sf, int64_t sh, int64_t sw, int64_t sc, void* stream);
+int mt_sf_stem_dgrad(const float* dz, int64_t ldz, const float* wt, float* dx, int N, int T, int H, int W, int kt, int K, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Launch plans (the caller side of the step: reference train.py:332-378, the Python loop that issues every op).

@@ -263,6 +263,31 @@ __global__ __launch_bounds__(256) void ingest_kernel(const TS* __restrict__ src,
   *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], 0.f);
 }
 
+// The ingest's adjoint: dsrc[b][f][h][w][c] = k * sum of dout_j[b][.][h][w][c] over the output frames j that selected f, in the order
+// jlist[start[f] .. start[f+1]) lists them (ascending j); a frame nobody selected gets 0.  One thread per source pixel: a gather.
+__global__ __launch_bounds__(256) void ingest_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ dout2,
+                                                         const int* __restrict__ start, const int* __restrict__ jlist, int F, int Tout,
+                                                         int Tsplit, int B, int H, int W, float k, int normalize, float* __restrict__ dsrc,
+                                                         int64_t sb, int64_t sf, int64_t sh, int64_t sw, int64_t sc) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)B * F * H * W) return;
+  const int64_t hw = (int64_t)H * W;
+  const int64_t p = i % hw;
+  const int w = (int)(p % W), h = (int)(p / W), f = (int)((i / hw) % F);
+  const int b = (int)(i / (hw * F));
+  float a[3] = {0.f, 0.f, 0.f};
+  for (int m = start[f]; m < start[f + 1]; ++m) {
+    const int j = jlist[m];
+    const float* s = j < Tsplit ? dout + (((int64_t)b * Tsplit + j) * hw + p) * 4
+                                : dout2 + (((int64_t)b * (Tout - Tsplit) + (j - Tsplit)) * hw + p) * 4;
+    const float4 v = *reinterpret_cast<const float4*>(s);
+    a[0] += v.x; a[1] += v.y; a[2] += v.z;
+  }
+  float* o = dsrc + b * sb + f * sf + h * sh + w * sw;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[c * sc] = normalize ? a[c] * k : a[c];
+}
+
 unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -372,4 +397,18 @@ extern "C" int mt_sf_ingest(const void* src, int is_u8, int64_t sb, int64_t sf, 
     hipLaunchKernelGGL(ingest_kernel<float>, grid, dim3(256), 0, st, (const float*)src, sb, sf, sh, sw, sc, fidx, Tout, Tsplit, B, H, W,
                        normalize, out, out2);
   return check_launch("mt_sf_ingest");
+}
+
+extern "C" int mt_sf_ingest_bwd(const float* dout, const float* dout2, const int* start, const int* jlist, int F, int Tout, int Tsplit, int B,
+                                int H, int W, int normalize, float* dsrc, int64_t sb, int64_t sf, int64_t sh, int64_t sw, int64_t sc,
+                                void* stream) {
+  if (!dout || !start || !jlist || !dsrc || F <= 0 || Tout <= 0 || B <= 0 || H <= 0 || W <= 0 || Tsplit <= 0 || Tsplit > Tout ||
+      (Tsplit < Tout && !dout2))
+    return fail(MT_ERR_ARG, "mt_sf_ingest_bwd: bad args");
+  if (((uintptr_t)dout | (uintptr_t)(dout2 ? dout2 : dout)) & 15)
+    return fail(MT_ERR_UNSUPPORTED, "mt_sf_ingest_bwd: dout and dout2 must be 16-byte aligned");
+  const float k = (float)(1.0 / (255.0 * 0.225));
+  hipLaunchKernelGGL(ingest_bwd_kernel, dim3(blocks((int64_t)B * F * H * W)), dim3(256), 0, (hipStream_t)stream, dout, dout2, start, jlist, F,
+                     Tout, Tsplit, B, H, W, k, normalize, dsrc, sb, sf, sh, sw, sc);
+  return check_launch("mt_sf_ingest_bwd");
 }

@@ -147,12 +147,15 @@ def baseline_eval_step(ex, model, batch):
 
 def input_gradient(ex, model, batch, pos_weight=None):
     """Gradient of the callers' loss with respect to the face crops: what saliency maps and FGSM / PGD perturbations are made of.
-    ex: EfficientNet-B0 or Xception; model: SizeInvariantTimeSformer (forward() above) or Baseline (baseline_forward()).
+    ex: EfficientNet-B0 or Xception; model: SizeInvariantTimeSformer (forward() above) or Baseline (baseline_forward()); a SlowFast
+    model goes to slowfast_input_gradient (ex is not used, pass None).
     Returns (logits, loss, dvideos) with dvideos.shape == batch["videos"].shape, fp32; nothing is added to any parameter's .grad.
     The modules run in the mode they are in (the saliency setting is eval() with every parameter requires_grad_(False); parameters
     that do require grad only cost their weight-gradient launches, and a train-mode extractor updates its BatchNorm running statistics
     as any forward does).  The extractor runs its eager launch sequence: recorded launch plans are neither used nor made.
     uint8 crops have no gradient: cast them first (`videos.float()`)."""
+    if isinstance(model, _slowfast.SlowFast):                                  # `--model 2` has no extractor: ex is ignored
+        return slowfast_input_gradient(model, batch["videos"], batch["labels"], pos_weight)
     videos = batch["videos"]
     if not torch.is_tensor(videos) or not videos.is_floating_point():
         raise ValueError(f"input_gradient: videos must be a floating-point tensor (got {getattr(videos, 'dtype', type(videos))}); "
@@ -160,7 +163,7 @@ def input_gradient(ex, model, batch, pos_weight=None):
     if not videos.is_cuda:
         raise ValueError("input_gradient: videos must be on the device (the extractors have no CPU path)")
     if not isinstance(model, (SizeInvariantTimeSformer, Baseline)):
-        raise TypeError(f"input_gradient: model must be a SizeInvariantTimeSformer or a Baseline, got {type(model).__name__}")
+        raise TypeError(f"input_gradient: model must be a SizeInvariantTimeSformer, a Baseline or a SlowFast, got {type(model).__name__}")
     x = videos.detach().requires_grad_(True)
     local = dict(batch, videos=x)
     with torch.enable_grad():
@@ -198,6 +201,25 @@ def slowfast_train_step(model, optimizer, videos, labels, pos_weight=None):
 def slowfast_eval_step(model, videos):
     """test.py:255-259 with `--model 2`: transform and eval forward; returns the logits."""
     return model(_slowfast.slowfast_input_transform(videos))
+
+
+def slowfast_input_gradient(model, videos, labels, pos_weight=None, **transform):
+    """Gradient of the `--model 2` loss with respect to the clips: videos [B, F, H, W, 3] or [B, 3, F, H, W], floating point, on the
+    device; `transform` goes to slowfast_input_transform (crop_size, side_size, num_frames).  Returns (logits, loss, dvideos) with
+    dvideos.shape == videos.shape, fp32: frames the subsampling selected several times (both pathways, repeats of a short clip) hold
+    the sum, frames it skipped hold 0.  Nothing is added to any parameter's .grad; the model runs in the mode it is in (the saliency
+    setting is eval() with every parameter requires_grad_(False)).  uint8 clips have no gradient: cast them first."""
+    if not torch.is_tensor(videos) or not videos.is_floating_point():
+        raise ValueError(f"slowfast_input_gradient: videos must be a floating-point tensor (got {getattr(videos, 'dtype', type(videos))}); "
+                         "cast uint8 clips with .float() first")
+    if not videos.is_cuda:
+        raise ValueError("slowfast_input_gradient: videos must be on the device (SlowFast has no CPU path)")
+    x = videos.detach().requires_grad_(True)
+    with torch.enable_grad():
+        logits = model(_slowfast.slowfast_input_transform(x, **transform))
+        loss = optim.bce_with_logits(logits, labels, pos_weight)
+        dvideos, = torch.autograd.grad(loss, x)
+    return logits.detach(), loss.detach(), dvideos.float()
 
 
 def aggregate_attentions(attentions, heads, num_frames, frames_per_identity, scale_factor=50000):

@@ -11,7 +11,9 @@ fusion kernel (7, 1, 1)) with pytorchvideo's module names, so the state-dict key
 The modules only hold parameters and settings; `SlowFast.forward` runs the whole network in the HIP library (slowfast_engine.py).
 
 Inputs: `forward([slow, fast])` with slow [B, 3, 8, H, W] and fast [B, 3, 32, H, W] (the reference's PackPathway output), or the pair
-`slowfast_input_transform(videos)` returns (device tensors that the network reads without a copy).
+`slowfast_input_transform(videos)` returns (device tensors that the network reads without a copy).  Pathway tensors or fp32 videos
+that require grad get their gradient through autograd (the stems' data gradient mt_sf_stem_dgrad, the ingest's adjoint
+mt_sf_ingest_bwd); without one nothing is recorded and the packing reads `x.detach()`.
 """
 import torch
 from torch import nn
@@ -180,6 +182,25 @@ def frame_indices(n_in, n_out):
     return [(i * (n_in - 1)) // (n_out - 1) for i in range(n_out)]
 
 
+def frame_sources(fidx, F):
+    """The inverse of a frame selection, CSR style: (start, j) with j[start[f]:start[f + 1]] = the output frames that selected source
+    frame f, ascending (the summation order of mt_sf_ingest_bwd); a frame nobody selected has an empty range."""
+    fidx = [int(f) for f in fidx]
+    if fidx and not 0 <= min(fidx) <= max(fidx) < F:
+        raise ValueError(f"frame index out of range for {F} frames")
+    start = [0] * (F + 1)
+    for f in fidx:
+        start[f + 1] += 1
+    for f in range(F):
+        start[f + 1] += start[f]
+    fill = list(start[:F])
+    js = [0] * len(fidx)
+    for j, f in enumerate(fidx):
+        js[fill[f]] = j
+        fill[f] += 1
+    return start, js
+
+
 def _packed_view(buf):
     """[B, T, H, W, 4] packed buffer -> the [B, 3, T, H, W] tensor the reference's transform returns (a view, no copy)."""
     v = buf[..., :3].permute(0, 4, 1, 2, 3)
@@ -212,6 +233,73 @@ def ingest(src, fidx, normalize, layout, split=None):
     return out if out2 is None else (out, out2)
 
 
+def _src_strides(src, layout):
+    """Element strides (b, f, h, w, c) of a clip tensor in either layout."""
+    return [src.stride(i) for i in ((0, 1, 2, 3, 4) if layout == "bfhwc" else (0, 2, 3, 4, 1))]
+
+
+_SOURCES = {}
+
+
+def _sources_on_device(fidx, F, device):
+    """frame_sources(fidx, F) as int32 device tensors, kept per selection (a training loop asks for the same one every step)."""
+    key = (fidx, F, str(device))
+    hit = _SOURCES.get(key)
+    if hit is None:
+        if len(_SOURCES) >= 64:
+            _SOURCES.clear()
+        start, js = frame_sources(list(fidx), F)
+        hit = _SOURCES[key] = (torch.tensor(start, dtype=torch.int32).to(device), torch.tensor(js, dtype=torch.int32).to(device))
+    return hit
+
+
+def ingest_bwd(dout, dout2, fidx, shape, normalize, layout, split=None):
+    """One mt_sf_ingest_bwd launch, the adjoint of ingest(): gradients of the packed buffers ([B, T, H, W, 4]; dout2 None without a
+    split) -> the fp32 gradient of the source clip of `shape` in `layout`."""
+    if layout == "bfhwc":
+        B, F, H, W, _ = shape
+    else:
+        B, _, F, H, W = shape
+    n = len(fidx)
+    split = n if split is None else split
+    want = [(B, split, H, W, 4)] + ([(B, n - split, H, W, 4)] if split < n else [])
+    got = [tuple(d.shape) for d in (dout, dout2) if d is not None]
+    if got != want:
+        raise ValueError(f"ingest_bwd: packed gradients of shapes {got}, expected {want}")
+    dout = dout.contiguous().float()
+    dout2 = dout2.contiguous().float() if dout2 is not None else None
+    dsrc = torch.empty(tuple(shape), dtype=torch.float32, device=dout.device)
+    st, jl = _sources_on_device(tuple(fidx), F, dout.device)
+    sb, sf, sh, sw, sc = _src_strides(dsrc, layout)
+    L.check(L.get().mt_sf_ingest_bwd(L.ptr(dout), L.ptr(dout2), L.ptr(st), L.ptr(jl), F, n, split, B, H, W, int(normalize), L.ptr(dsrc),
+                                     sb, sf, sh, sw, sc, L.stream_ptr()), "mt_sf_ingest_bwd")
+    return dsrc
+
+
+class _Ingest(torch.autograd.Function):
+    """ingest() of an fp32 clip that requires grad; the backward is mt_sf_ingest_bwd."""
+
+    @staticmethod
+    def forward(ctx, src, fidx, normalize, layout, split):
+        ctx.meta = (tuple(fidx), tuple(src.shape), bool(normalize), layout, split)
+        out = ingest(src, fidx, normalize, layout, split)
+        return out if isinstance(out, tuple) else (out,)
+
+    @staticmethod
+    def backward(ctx, *g):
+        fidx, shape, normalize, layout, split = ctx.meta
+        n = len(fidx)
+        sizes = [n] if split is None or split == n else [split, n - split]
+        B, H, W = (shape[0], shape[2], shape[3]) if layout == "bfhwc" else (shape[0], shape[3], shape[4])
+        g = [gi if gi is not None else torch.zeros(B, t, H, W, 4, dtype=torch.float32, device=next(x for x in g if x is not None).device)
+             for gi, t in zip(g, sizes)]
+        return ingest_bwd(g[0], g[1] if len(g) > 1 else None, list(fidx), shape, normalize, layout, split), None, None, None, None
+
+
+def _wants_grad(x):
+    return torch.is_grad_enabled() and x.is_floating_point() and x.requires_grad
+
+
 def slowfast_input_transform(videos, crop_size=256, side_size=256, num_frames=NUM_FRAMES, device=None):
     """utils.py:166-186 for a batch: `videos` [B, F, H, W, 3] (the loader's layout) or [B, 3, F, H, W] (after train.py:357's
     rearrange), uint8 or fp32.  Returns [slow [B, 3, 8, H, W], fast [B, 3, 32, H, W]] on the device, as train.py:358 builds them:
@@ -232,20 +320,28 @@ def slowfast_input_transform(videos, crop_size=256, side_size=256, num_frames=NU
     F = videos.shape[1] if layout == "bfhwc" else videos.shape[2]
     fi = frame_indices(F, num_frames)
     si = frame_indices(num_frames, num_frames // ALPHA)
-    slow, fast = ingest(videos, [fi[j] for j in si] + fi, True, layout, split=len(si))
+    sel = [fi[j] for j in si] + fi
+    if _wants_grad(videos):             # fp32 videos that require grad: the packing is part of the graph (uint8 has no gradient)
+        slow, fast = _Ingest.apply(videos.float(), sel, True, layout, len(si))
+    else:
+        slow, fast = ingest(videos, sel, True, layout, split=len(si))
     return [_packed_view(slow), _packed_view(fast)]
 
 
 def pack_pathway_input(x):
     """A pathway input [B, 3, T, H, W] -> packed [B, T, H, W, 4] (no copy when it came from slowfast_input_transform)."""
     buf = getattr(x, "_mt_packed", None)
-    if buf is not None and buf.is_cuda:
+    # the transform's buffer serves as it is unless a gradient is asked of a view whose buffer has no history (requires_grad_() on the
+    # transform's outputs of uint8 videos, or of a no_grad transform): that view is then packed again, inside the graph
+    if buf is not None and buf.is_cuda and (buf.requires_grad or not _wants_grad(x)):
         return buf
     if not x.is_cuda:
         raise L.MintimeHipError("SlowFast (MI355X build) needs device tensors; there is no CPU path")
     if x.dim() != 5 or x.shape[1] != 3:
         raise ValueError(f"expected a [B, 3, T, H, W] pathway input, got {tuple(x.shape)}")
+    if _wants_grad(x):
+        return _Ingest.apply(x.float(), list(range(x.shape[2])), False, "bcfhw", None)[0]
     return ingest(x.detach(), list(range(x.shape[2])), False, "bcfhw")
 
 
-__all__ = ["SlowFast", "slowfast_r50", "slowfast_input_transform", "frame_indices"]
+__all__ = ["SlowFast", "slowfast_r50", "slowfast_input_transform", "frame_indices", "frame_sources"]

@@ -105,6 +105,21 @@ def conv_dgrad(x, dz, w, conv, out, accumulate):
             "mt_conv3d_dgrad")
 
 
+def _pack_w_stem_dgrad(w):
+    """torch stem weight [K, 3, kt, 7, 7] -> [kt*K, 160]: row dt*K + co, column (kh*7 + kw)*3 + c, columns 147..159 zero (the operand
+    of mt_sf_stem_dgrad)."""
+    wt = w.detach().permute(2, 0, 3, 4, 1).reshape(w.shape[2] * w.shape[0], -1)
+    return torch.nn.functional.pad(wt, (0, 160 - wt.shape[1])).contiguous()
+
+
+def stem_dgrad(x, dz, w):
+    """The stem's data gradient down to the packed clip: dz = dL/dz of the stem convolution of x -> dL/dx as [N, T, H, W, 4]."""
+    dx = torch.empty(x.N, x.T, x.H, x.W, 4, dtype=torch.float32, device=dz.t.device)
+    L.check(L.get().mt_sf_stem_dgrad(L.ptr(dz.t), dz.ld, L.ptr(_pack_w_stem_dgrad(w)), L.ptr(dx), x.N, x.T, x.H, x.W, w.shape[2],
+                                     w.shape[0], L.stream_ptr()), "mt_sf_stem_dgrad")
+    return dx
+
+
 class BN:
     """Folded BatchNorm of one layer: scale, shift, mean_invstd."""
     __slots__ = ("key", "scale", "shift", "mi", "count", "training")
@@ -281,13 +296,15 @@ def _stem_fwd(ctx, key, x, kt, out):
     return Fm(out, z.N, z.T, Ho, Wo), (conv, x, z, b, arg)
 
 
-def _stem_bwd(ctx, rec, gp):
+def _stem_bwd(ctx, rec, gp, want_dx=False):
+    """Adjoint of the stem from gp = dL/d(pool output); want_dx: also returns dL/d(clip) as a packed [N, T, H, W, 4] tensor."""
     conv, x, z, b, arg = rec
     din = torch.empty(z.rows, z.C, dtype=torch.float32, device=z.t.device)
     L.check(L.get().mt_sf_maxpool_bwd(L.ptr(gp.t), gp.ld, L.ptr(arg), L.ptr(din), z.N * z.T, z.H, z.W, z.C, L.stream_ptr()),
             "mt_sf_maxpool_bwd")
     dz = bn_bwd(ctx, b, Fm(din, z.N, z.T, z.H, z.W), z, relu_bn=b, out=din)
     ctx.add_wgrad(conv.key, x, None, dz, conv)
+    return stem_dgrad(x, dz, ctx.P[conv.key + ".weight"]) if want_dx else None
 
 
 def _dropout_mult(model, B, P, dev):
@@ -369,7 +386,8 @@ def network_forward(ctx, model, xs, xf):
     return logits, recs
 
 
-def network_backward(ctx, recs, g):
+def network_backward(ctx, recs, g, need_x=(False, False)):
+    """The reverse walk; need_x: return dL/d(packed slow clip), dL/d(packed fast clip) where asked for (else None)."""
     lib = L.get()
     dev = g.device
     xsl, xfa, d, mult, Pn, ((kts, khs, kws), (ktf, khf, kwf)) = recs["head"]
@@ -401,15 +419,16 @@ def network_backward(ctx, recs, g):
             gfa = Fm(gx, r.x.N, r.x.T, r.x.H, r.x.W)
     rs_stem, rf_stem, rfus, ps = recs["stem"]
     _fusion_bwd(ctx, rfus, gsl.t, S.STEM_OUT[0], gfa.t)
-    _stem_bwd(ctx, rs_stem, Fm(gsl.t[:, :S.STEM_OUT[0]], gsl.N, gsl.T, gsl.H, gsl.W))
-    _stem_bwd(ctx, rf_stem, gfa)
+    dxs = _stem_bwd(ctx, rs_stem, Fm(gsl.t[:, :S.STEM_OUT[0]], gsl.N, gsl.T, gsl.H, gsl.W), need_x[0])
+    dxf = _stem_bwd(ctx, rf_stem, gfa, need_x[1])
+    return dxs, dxf
 
 
 class _SlowFastFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, mode, xs_buf, xf_buf, *params):
         grad_on, names, training = mode
-        save = grad_on and any(ctx.needs_input_grad[4:])
+        save = grad_on and any(ctx.needs_input_grad[2:])
         walk = _Walk(model, names, params, training)
         B, Ts, H, W, _ = xs_buf.shape
         Tf = xf_buf.shape[1]
@@ -430,12 +449,12 @@ class _SlowFastFunction(torch.autograd.Function):
         walk = ctx.walk
         need = ctx.needs_input_grad[4:]
         walk.need = {n: bool(r) for n, r in zip(walk.names, need)}
-        network_backward(walk, ctx.recs, dlogits.contiguous().float())
+        dxs, dxf = network_backward(walk, ctx.recs, dlogits.contiguous().float(), ctx.needs_input_grad[2:4])
         ctx.recs = None
         out = []
         for n, r in zip(walk.names, need):
             out.append(walk.grads.get(n) if r else None)
-        return (None, None, None, None, *out)
+        return (None, None, dxs, dxf, *out)
 
 
 def _named_params(model):
