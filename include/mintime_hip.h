@@ -618,6 +618,24 @@ int mt_baseline_head_bwd(const float* dlogits, const float* pooled, const float*
  *   k = 1 / (255 * 0.225) (normalize) or 1.  The inverse map comes CSR style: start (int32 [F + 1]) and jlist (int32 [Tout], j
  *   ascending inside a frame): frame f sums jlist[start[f] .. start[f+1]) in that order, a frame nobody selected gets exact 0.
  *   dsrc is fp32 with the element strides (b, f, h, w, c) of mt_sf_ingest's src; written, one writer per element.
+ * mt_sf_ingest_resize (csrc/sf_resize.hip): mt_sf_ingest with the reference's two spatial steps between Normalize and PackPathway:
+ *   ShortSideScale (bilinear, align_corners = False, no antialiasing) of the Hs x Ws source frames to Hr x Wr and CenterCropVideo to
+ *   the window [top, top + Ho) x [left, left + Wo).  out [B][Tsplit][Ho][Wo][4] / out2 [B][Tout - Tsplit][Ho][Wo][4], 4th channel 0.
+ *   The caller gives the taps of the WINDOW's rows and columns (window index d <-> resized index top + d, left + d): hidx (int32
+ *   [2][Ho]: source rows i0, then i1) and hlam (fp32 [Ho]); widx ([2][Wo]) and wlam ([Wo]) likewise.  Per channel, with
+ *   v = (u / 255 - 0.45) / 0.225 (normalize) or u taken of every tap BEFORE the interpolation (the reference's order):
+ *     out = (1 - hlam) ((1 - wlam) v[i0h][i0w] + wlam v[i0h][i1w]) + hlam ((1 - wlam) v[i1h][i0w] + wlam v[i1h][i1w])
+ *   Table indices are clamped to the source frame before they address it.  Hr, Wr, top, left only say what the tables were made
+ *   for: a window outside the resized frame returns MT_ERR_ARG.
+ * mt_sf_ingest_resize_bwd: its exact adjoint as a gather, dsrc as mt_sf_ingest_bwd's (fp32, the source's strides, written, one writer
+ *   per element, k as there):  dsrc[b][f][hs][ws][c] = k * sum hwt[r] * wwt[q] * dout_j[b][.][hout[r]][wout[q]][c]  over the output
+ *   frames j = jlist[fstart[f] .. fstart[f+1]), the row references r in [hstart[hs], hstart[hs+1]) and the column references q in
+ *   [wstart[ws], wstart[ws+1]), in that nesting and in list order.  hstart (int32 [Hs + 1]), hout (int32: window row) and hwt
+ *   (fp32: 1 - hlam for a reference as i0, hlam as i1; a clamped edge with i1 == i0 lists both) are the inverse of hidx / hlam, CSR
+ *   style; wstart, wout, wwt likewise.  A frame nobody selected, a pixel outside the window's footprint and any element no tap
+ *   references get exact 0.
+ *   Both: MT_ERR_ARG for a null pointer, an empty shape or a window outside the resized frame; MT_ERR_UNSUPPORTED, before any
+ *   launch, for packed buffers that are not 16-byte aligned (and for more than 65535 clips or frames).
  * mt_sf_stem_dgrad: the stems' data gradient down to the clip (csrc/sf_stem_dgrad.hip), with Ho = (H-1)/2 + 1, Wo = (W-1)/2 + 1:
  *   dx[n][t][h][w][c] = sum_{dt,kh,kw,co} dz[n][t + kt/2 - dt][(h+3-kh)/2][(w+3-kw)/2][co] * w[co][c][dt][kh][kw] over the taps with
  *   even h+3-kh and w+3-kw and a dz index on the grid.  dz [N][T][Ho][Wo] rows of K floats, pitch ldz (% 4 == 0), 16-byte aligned;
@@ -659,6 +677,13 @@ int mt_sf_ingest(const void* src, int is_u8, int64_t sb, int64_t sf, int64_t sh,
                  int Tsplit, int B, int H, int W, int normalize, float* out, float* out2, void* stream);
 int mt_sf_ingest_bwd(const float* dout, const float* dout2, const int* start, const int* jlist, int F, int Tout, int Tsplit, int B, int H,
                      int W, int normalize, float* dsrc, int64_t sb, int64_t sf, int64_t sh, int64_t sw, int64_t sc, void* stream);
+int mt_sf_ingest_resize(const void* src, int is_u8, int64_t sb, int64_t sf, int64_t sh, int64_t sw, int64_t sc, const int* fidx, int Tout,
+                        int Tsplit, int B, int Hs, int Ws, const int* hidx, const float* hlam, const int* widx, const float* wlam, int Hr,
+                        int Wr, int top, int left, int Ho, int Wo, int normalize, float* out, float* out2, void* stream);
+int mt_sf_ingest_resize_bwd(const float* dout, const float* dout2, const int* fstart, const int* jlist, int F, int Tout, int Tsplit, int B,
+                            int Hs, int Ws, const int* hstart, const int* hout, const float* hwt, const int* wstart, const int* wout,
+                            const float* wwt, int Hr, int Wr, int top, int left, int Ho, int Wo, int normalize, float* dsrc, int64_t sb,
+                            int64_t sf, int64_t sh, int64_t sw, int64_t sc, void* stream);
 int mt_sf_stem_dgrad(const float* dz, int64_t ldz, const float* wt, float* dx, int N, int T, int H, int W, int kt, int K, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

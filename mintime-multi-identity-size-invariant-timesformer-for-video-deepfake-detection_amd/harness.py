@@ -185,10 +185,10 @@ def build_slowfast(seed=0, device="cuda", head_pool_kernel_sizes=((8, 7, 7), (32
     return model, opt
 
 
-def slowfast_train_step(model, optimizer, videos, labels, pos_weight=None):
+def slowfast_train_step(model, optimizer, videos, labels, pos_weight=None, **transform):
     """One `--model 2` optimisation step (train.py:356-378): input transform, forward, BCE-with-logits, SGD.  videos [B, F, H, W, 3]
-    (uint8 or fp32), labels [B]."""
-    x = _slowfast.slowfast_input_transform(videos)
+    (uint8 or fp32), labels [B]; `transform` goes to slowfast_input_transform (crop_size, side_size, num_frames, interpolation)."""
+    x = _slowfast.slowfast_input_transform(videos, **transform)
     y_pred = model(x)
     loss = optim.bce_with_logits(y_pred, labels, pos_weight)
     optimizer.zero_grad(set_to_none=True)
@@ -198,17 +198,18 @@ def slowfast_train_step(model, optimizer, videos, labels, pos_weight=None):
 
 
 @torch.no_grad()
-def slowfast_eval_step(model, videos):
-    """test.py:255-259 with `--model 2`: transform and eval forward; returns the logits."""
-    return model(_slowfast.slowfast_input_transform(videos))
+def slowfast_eval_step(model, videos, **transform):
+    """test.py:255-259 with `--model 2`: transform (`transform` goes to slowfast_input_transform) and eval forward; returns the logits."""
+    return model(_slowfast.slowfast_input_transform(videos, **transform))
 
 
 def slowfast_input_gradient(model, videos, labels, pos_weight=None, **transform):
     """Gradient of the `--model 2` loss with respect to the clips: videos [B, F, H, W, 3] or [B, 3, F, H, W], floating point, on the
-    device; `transform` goes to slowfast_input_transform (crop_size, side_size, num_frames).  Returns (logits, loss, dvideos) with
-    dvideos.shape == videos.shape, fp32: frames the subsampling selected several times (both pathways, repeats of a short clip) hold
-    the sum, frames it skipped hold 0.  Nothing is added to any parameter's .grad; the model runs in the mode it is in (the saliency
-    setting is eval() with every parameter requires_grad_(False)).  uint8 clips have no gradient: cast them first."""
+    device; `transform` goes to slowfast_input_transform (crop_size, side_size, num_frames, interpolation).  Returns (logits, loss,
+    dvideos) with dvideos.shape == videos.shape, fp32: frames the subsampling selected several times (both pathways, repeats of a short
+    clip) hold the sum, frames it skipped and pixels outside a centre crop's footprint hold 0.  Nothing is added to any
+    parameter's .grad; the model runs in the mode it is in (the saliency setting is eval() with every parameter requires_grad_(False)).
+    uint8 clips have no gradient: cast them first."""
     if not torch.is_tensor(videos) or not videos.is_floating_point():
         raise ValueError(f"slowfast_input_gradient: videos must be a floating-point tensor (got {getattr(videos, 'dtype', type(videos))}); "
                          "cast uint8 clips with .float() first")

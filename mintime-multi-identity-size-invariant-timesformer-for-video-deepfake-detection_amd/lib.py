@@ -178,6 +178,10 @@ PROTOTYPES = {
     "mt_sf_head_dfeat": [f32p, f32p, i64] + [C.c_int] * 10 + [C.c_void_p],
     "mt_sf_ingest": [C.c_void_p, C.c_int, i64, i64, i64, i64, i64, C.c_void_p] + [C.c_int] * 6 + [f32p, f32p, C.c_void_p],
     "mt_sf_ingest_bwd": [f32p, f32p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [f32p, i64, i64, i64, i64, i64, C.c_void_p],
+    "mt_sf_ingest_resize": [C.c_void_p, C.c_int, i64, i64, i64, i64, i64, C.c_void_p] + [C.c_int] * 5 +
+                           [C.c_void_p, f32p, C.c_void_p, f32p] + [C.c_int] * 7 + [f32p, f32p, C.c_void_p],
+    "mt_sf_ingest_resize_bwd": [f32p, f32p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, f32p] * 2 + [C.c_int] * 7 +
+                               [f32p, i64, i64, i64, i64, i64, C.c_void_p],
     "mt_sf_stem_dgrad": [f32p, i64, f32p, f32p] + [C.c_int] * 6 + [C.c_void_p],
     "mt_plan_create": [C.POINTER(C.c_void_p)],
     "mt_plan_destroy": [C.c_void_p],

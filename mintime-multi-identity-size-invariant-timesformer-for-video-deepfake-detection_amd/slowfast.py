@@ -13,8 +13,11 @@ The modules only hold parameters and settings; `SlowFast.forward` runs the whole
 Inputs: `forward([slow, fast])` with slow [B, 3, 8, H, W] and fast [B, 3, 32, H, W] (the reference's PackPathway output), or the pair
 `slowfast_input_transform(videos)` returns (device tensors that the network reads without a copy).  Pathway tensors or fp32 videos
 that require grad get their gradient through autograd (the stems' data gradient mt_sf_stem_dgrad, the ingest's adjoint
-mt_sf_ingest_bwd); without one nothing is recorded and the packing reads `x.detach()`.
+mt_sf_ingest_bwd, or mt_sf_ingest_resize_bwd when the transform resizes and crops); without one nothing is recorded and the packing
+reads `x.detach()`.
 """
+import math
+
 import torch
 from torch import nn
 
@@ -296,35 +299,223 @@ class _Ingest(torch.autograd.Function):
         return ingest_bwd(g[0], g[1] if len(g) > 1 else None, list(fidx), shape, normalize, layout, split), None, None, None, None
 
 
+# ---- ShortSideScale + CenterCropVideo (reference utils.py:176-177) ------------------------------------------------------------------
+# The size rule is pytorchvideo's short_side_scale and the crop rounding torchvision's center_crop, restated from their published
+# source and not checked against either package.  The interpolation itself is checked against F.interpolate.
+
+def resize_geometry(H, W, side_size, crop_size):
+    """(Hr, Wr, top, left): the frame size after ShortSideScale(side_size) of H x W frames and the corner of the
+    CenterCropVideo(crop_size) window in it.  The short side becomes side_size, the long one floor(long / short * side_size); the
+    corner is Python's round((size - crop_size) / 2.0), halves to the even integer."""
+    if W < H:
+        Hr, Wr = int(math.floor(float(H) / W * side_size)), side_size
+    else:
+        Hr, Wr = side_size, int(math.floor(float(W) / H * side_size))
+    if Hr < crop_size or Wr < crop_size:
+        raise ValueError("height and width must be no smaller than crop_size")
+    return Hr, Wr, int(round((Hr - crop_size) / 2.0)), int(round((Wr - crop_size) / 2.0))
+
+
+def axis_taps(n_in, n_out, first=0, count=None, dtype=torch.float32):
+    """The two taps of bilinear interpolation (align_corners=False, no antialiasing) along one axis, n_in -> n_out, for the `count`
+    output indices from `first` on (default: all): (i0, i1, lam) as CPU tensors (int32, int32, dtype), with
+    value[first + d] = (1 - lam[d]) * x[i0[d]] + lam[d] * x[i1[d]].  Computed in `dtype` the way F.interpolate does in that dtype."""
+    count = n_out - first if count is None else count
+    d = torch.arange(first, first + count, dtype=dtype)
+    scale = torch.tensor(float(n_in), dtype=dtype) / n_out
+    src = (scale * (d + 0.5) - 0.5).clamp_min(0)
+    i0 = src.floor().long().clamp_max(n_in - 1)
+    i1 = (i0 + 1).clamp_max(n_in - 1)
+    lam = (src - i0.to(dtype)).clamp(0, 1)
+    return i0.int(), i1.int(), lam
+
+
+def axis_sources(i0, i1, lam, n_in):
+    """The inverse of axis_taps, CSR style: (start, out, wt) with out[start[s]:start[s + 1]] = the output indices that reference
+    source index s and wt their weights (1 - lam as i0, lam as i1), output index ascending, i0 before i1 (the summation order of
+    mt_sf_ingest_resize_bwd).  A clamped edge (i1 == i0) lists both weights; a weight of exactly 0 references nothing."""
+    w0, w1 = (1 - lam).tolist(), lam.tolist()
+    refs = [[] for _ in range(n_in)]
+    for d, (a, b) in enumerate(zip(i0.tolist(), i1.tolist())):
+        if w0[d] != 0:
+            refs[a].append((d, w0[d]))
+        if w1[d] != 0:
+            refs[b].append((d, w1[d]))
+    start = [0]
+    for r in refs:
+        start.append(start[-1] + len(r))
+    return start, [d for r in refs for d, _ in r], [w for r in refs for _, w in r]
+
+
+_RESIZE_TABLES = {}
+
+
+def _resize_tables(Hs, Ws, geom, device):
+    """Device tables of one geometry (Hr, Wr, top, left, Ho, Wo) of Hs x Ws frames, kept like _sources_on_device: per axis the forward's
+    (idx [2][n] int32, lam [n] fp32) and the backward's (start, out, wt), all from one fp32 axis_taps table."""
+    key = (Hs, Ws, tuple(geom), str(device))
+    hit = _RESIZE_TABLES.get(key)
+    if hit is None:
+        if len(_RESIZE_TABLES) >= 64:
+            _RESIZE_TABLES.clear()
+        Hr, Wr, top, left, Ho, Wo = geom
+        hit = []
+        for n_in, n_out, first, count in ((Hs, Hr, top, Ho), (Ws, Wr, left, Wo)):
+            i0, i1, lam = axis_taps(n_in, n_out, first, count)
+            start, out, wt = axis_sources(i0, i1, lam, n_in)
+            hit += [torch.stack([i0, i1]).to(device), lam.to(device), torch.tensor(start, dtype=torch.int32).to(device),
+                    torch.tensor(out, dtype=torch.int32).to(device), torch.tensor(wt, dtype=torch.float32).to(device)]
+        hit = _RESIZE_TABLES[key] = tuple(hit)
+    return hit
+
+
+def _dense(shape, strides):
+    """True when the strides address every element of one block of prod(shape) elements once: a permutation of a contiguous tensor."""
+    expect = 1
+    for s, n in sorted((s, n) for n, s in zip(shape, strides) if n != 1):
+        if s != expect:
+            return False
+        expect *= n
+    return True
+
+
+def _check_geometry(geom):
+    Hr, Wr, top, left, Ho, Wo = geom
+    if Hr < Ho or Wr < Wo:
+        raise ValueError("height and width must be no smaller than crop_size")
+
+
+def ingest_resize(src, fidx, normalize, layout, geom, split=None):
+    """One mt_sf_ingest_resize launch: ingest() with the frames resized (bilinear) to geom's Hr x Wr and cropped to its Ho x Wo
+    window at (top, left); geom = (Hr, Wr, top, left, Ho, Wo).  Packed [B, T, Ho, Wo, 4] buffers as ingest() returns them."""
+    _check_geometry(geom)
+    if layout == "bfhwc":
+        B, F, H, W, _ = src.shape
+    else:
+        B, _, F, H, W = src.shape
+    if max(fidx) >= F:
+        raise ValueError(f"frame index {max(fidx)} out of range for {F} frames")
+    is_u8 = src.dtype == torch.uint8
+    if not is_u8 and src.dtype != torch.float32:
+        src = src.float()
+    sb, sf, sh, sw, sc = _src_strides(src, layout)
+    Hr, Wr, top, left, Ho, Wo = geom
+    n = len(fidx)
+    split = n if split is None else split
+    out = torch.empty(B, split, Ho, Wo, 4, dtype=torch.float32, device=src.device)
+    out2 = torch.empty(B, n - split, Ho, Wo, 4, dtype=torch.float32, device=src.device) if split < n else None
+    idx = torch.tensor(fidx, dtype=torch.int32).to(src.device)
+    t = _resize_tables(H, W, geom, src.device)
+    L.check(L.get().mt_sf_ingest_resize(L.ptr(src), int(is_u8), sb, sf, sh, sw, sc, L.ptr(idx), n, split, B, H, W, L.ptr(t[0]), L.ptr(t[1]),
+                                        L.ptr(t[5]), L.ptr(t[6]), Hr, Wr, top, left, Ho, Wo, int(normalize), L.ptr(out), L.ptr(out2),
+                                        L.stream_ptr()), "mt_sf_ingest_resize")
+    return out if out2 is None else (out, out2)
+
+
+def ingest_resize_bwd(dout, dout2, fidx, shape, normalize, layout, geom, split=None, strides=None):
+    """One mt_sf_ingest_resize_bwd launch, the adjoint of ingest_resize(): gradients of the packed buffers ([B, T, Ho, Wo, 4]) -> the
+    fp32 gradient of the source clip of `shape` in `layout`, contiguous or with the given `strides` (those of a dense source, e.g. the
+    permuted view of train.py:357: the gradient is then written in the source's own memory order)."""
+    _check_geometry(geom)
+    if layout == "bfhwc":
+        B, F, H, W, _ = shape
+    else:
+        B, _, F, H, W = shape
+    Hr, Wr, top, left, Ho, Wo = geom
+    n = len(fidx)
+    split = n if split is None else split
+    want = [(B, split, Ho, Wo, 4)] + ([(B, n - split, Ho, Wo, 4)] if split < n else [])
+    got = [tuple(d.shape) for d in (dout, dout2) if d is not None]
+    if got != want:
+        raise ValueError(f"ingest_resize_bwd: packed gradients of shapes {got}, expected {want}")
+    dout = dout.contiguous().float()
+    dout2 = dout2.contiguous().float() if dout2 is not None else None
+    if strides is None:
+        dsrc = torch.empty(tuple(shape), dtype=torch.float32, device=dout.device)
+    else:
+        if not _dense(shape, strides):
+            raise ValueError(f"ingest_resize_bwd: strides {tuple(strides)} are not those of a dense tensor of shape {tuple(shape)}")
+        dsrc = torch.empty_strided(tuple(shape), tuple(strides), dtype=torch.float32, device=dout.device)
+    st, jl = _sources_on_device(tuple(fidx), F, dout.device)
+    t = _resize_tables(H, W, geom, dout.device)
+    sb, sf, sh, sw, sc = _src_strides(dsrc, layout)
+    L.check(L.get().mt_sf_ingest_resize_bwd(L.ptr(dout), L.ptr(dout2), L.ptr(st), L.ptr(jl), F, n, split, B, H, W, L.ptr(t[2]), L.ptr(t[3]),
+                                            L.ptr(t[4]), L.ptr(t[7]), L.ptr(t[8]), L.ptr(t[9]), Hr, Wr, top, left, Ho, Wo, int(normalize),
+                                            L.ptr(dsrc), sb, sf, sh, sw, sc, L.stream_ptr()), "mt_sf_ingest_resize_bwd")
+    return dsrc
+
+
+class _IngestResize(torch.autograd.Function):
+    """ingest_resize() of an fp32 clip that requires grad; the backward is mt_sf_ingest_resize_bwd."""
+
+    @staticmethod
+    def forward(ctx, src, fidx, normalize, layout, geom, split):
+        strides = tuple(src.stride()) if _dense(src.shape, src.stride()) else None          # the gradient follows a dense source's layout
+        ctx.meta = (tuple(fidx), tuple(src.shape), bool(normalize), layout, tuple(geom), split, strides)
+        out = ingest_resize(src, fidx, normalize, layout, geom, split)
+        return out if isinstance(out, tuple) else (out,)
+
+    @staticmethod
+    def backward(ctx, *g):
+        fidx, shape, normalize, layout, geom, split, strides = ctx.meta
+        n = len(fidx)
+        sizes = [n] if split is None or split == n else [split, n - split]
+        device = next(x for x in g if x is not None).device
+        g = [gi if gi is not None else torch.zeros(shape[0], t, geom[4], geom[5], 4, dtype=torch.float32, device=device)
+             for gi, t in zip(g, sizes)]
+        return (ingest_resize_bwd(g[0], g[1] if len(g) > 1 else None, list(fidx), shape, normalize, layout, geom, split, strides),
+                None, None, None, None, None)
+
+
 def _wants_grad(x):
     return torch.is_grad_enabled() and x.is_floating_point() and x.requires_grad
 
 
-def slowfast_input_transform(videos, crop_size=256, side_size=256, num_frames=NUM_FRAMES, device=None):
+INTERPOLATIONS = ("bilinear",)
+
+
+def slowfast_input_transform(videos, crop_size=256, side_size=256, num_frames=NUM_FRAMES, device=None, interpolation=None):
     """utils.py:166-186 for a batch: `videos` [B, F, H, W, 3] (the loader's layout) or [B, 3, F, H, W] (after train.py:357's
-    rearrange), uint8 or fp32.  Returns [slow [B, 3, 8, H, W], fast [B, 3, 32, H, W]] on the device, as train.py:358 builds them:
-    UniformTemporalSubsample(32), /255, Normalize(0.45, 0.225), PackPathway.  ShortSideScale(256) and CenterCrop(256) are identities
-    at the configured 256 x 256 (config/slowfast.yaml); other sizes are not supported."""
+    rearrange; the permuted view is read in place), uint8 or fp32, contiguous or strided.  Returns [slow [B, 3, 8, crop, crop],
+    fast [B, 3, 32, crop, crop]] on the device, as train.py:358 builds them: UniformTemporalSubsample(32), /255, Normalize(0.45, 0.225),
+    ShortSideScale(side_size), CenterCropVideo(crop_size), PackPathway -- one launch.
+
+    interpolation=None (default): the two spatial steps are only accepted where they are identities, side_size x side_size frames with
+    crop_size == side_size (the configured 256 x 256 of config/slowfast.yaml); anything else raises NotImplementedError.
+    interpolation="bilinear" (the name is pytorchvideo's ShortSideScale(interpolation=...) argument): frames of any size.  The short
+    side is scaled to side_size with F.interpolate(mode="bilinear", align_corners=False) arithmetic, no antialiasing, every tap
+    normalised before it is interpolated (the reference's order); the crop window's corner is resize_geometry()'s.  A crop larger
+    than the resized frame raises ValueError, as torchvision does.  Frames that need neither step take the same launch, and give the
+    same bits, as interpolation=None.  fp32 videos that require grad get their gradient through either path (uint8 has none)."""
     if not torch.is_tensor(videos) or videos.dim() != 5:
         raise ValueError("slowfast_input_transform: expected a [B, F, H, W, 3] or [B, 3, F, H, W] tensor")
+    if interpolation is not None and interpolation not in INTERPOLATIONS:
+        raise NotImplementedError(f"slowfast_input_transform: interpolation={interpolation!r} is not implemented; the supported mode is "
+                                  "'bilinear' (align_corners=False, no antialiasing)")
     layout = "bfhwc" if videos.shape[-1] == 3 else "bcfhw"
     if layout == "bcfhw" and videos.shape[1] != 3:
         raise ValueError(f"slowfast_input_transform: no 3-channel axis in {tuple(videos.shape)}")
     H, W = (videos.shape[2], videos.shape[3]) if layout == "bfhwc" else (videos.shape[3], videos.shape[4])
+    geom = None
     if not (H == W == crop_size == side_size):
-        raise NotImplementedError(f"slowfast_input_transform: ShortSideScale({side_size}) + CenterCrop({crop_size}) are only the identity "
-                                  f"for {side_size} x {side_size} frames (config/slowfast.yaml); got {H} x {W} -- the resize is not "
-                                  "implemented")
+        if interpolation is None:
+            raise NotImplementedError(f"slowfast_input_transform: ShortSideScale({side_size}) + CenterCrop({crop_size}) are only the "
+                                      f"identity for {side_size} x {side_size} frames (config/slowfast.yaml); got {H} x {W} -- pass "
+                                      "interpolation='bilinear' for the resize")
+        geom = resize_geometry(H, W, side_size, crop_size) + (crop_size, crop_size)
     if not videos.is_cuda:
         videos = videos.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
     F = videos.shape[1] if layout == "bfhwc" else videos.shape[2]
     fi = frame_indices(F, num_frames)
     si = frame_indices(num_frames, num_frames // ALPHA)
     sel = [fi[j] for j in si] + fi
-    if _wants_grad(videos):             # fp32 videos that require grad: the packing is part of the graph (uint8 has no gradient)
-        slow, fast = _Ingest.apply(videos.float(), sel, True, layout, len(si))
+    grad = _wants_grad(videos)          # fp32 videos that require grad: the packing is part of the graph (uint8 has no gradient)
+    if geom is None:
+        slow, fast = _Ingest.apply(videos.float(), sel, True, layout, len(si)) if grad else ingest(videos, sel, True, layout, split=len(si))
+    elif grad:
+        slow, fast = _IngestResize.apply(videos.float(), sel, True, layout, geom, len(si))
     else:
-        slow, fast = ingest(videos, sel, True, layout, split=len(si))
+        slow, fast = ingest_resize(videos, sel, True, layout, geom, split=len(si))
     return [_packed_view(slow), _packed_view(fast)]
 
 
@@ -344,4 +535,5 @@ def pack_pathway_input(x):
     return ingest(x.detach(), list(range(x.shape[2])), False, "bcfhw")
 
 
-__all__ = ["SlowFast", "slowfast_r50", "slowfast_input_transform", "frame_indices", "frame_sources"]
+__all__ = ["SlowFast", "slowfast_r50", "slowfast_input_transform", "frame_indices", "frame_sources", "resize_geometry", "axis_taps",
+           "axis_sources"]
