@@ -15,13 +15,6 @@ namespace {
 constexpr int kChunk = 256;    // channels per block of the pooling kernel
 constexpr int kSlab = 32;      // crops per partial sum of the backward reduction
 
-// butterfly sum over the 64 lanes: every lane ends with the same value (IEEE addition is commutative), in a fixed order
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // vc[c] = sum_j W1[j][c] w2[j] (c < C);  vc[C] = sum_j b1[j] w2[j] + b2.  Block = 64 columns x 16 groups of consecutive rows j (the
 // lanes read 64 consecutive floats of a row of W1); the group sums are added in group order.  (4 groups: 52 us per call at C = 1280,
 // m = 512 -- too few wavefronts, each a long chain of dependent loads.)

@@ -1,4 +1,4 @@
-// Shared host-side helpers for the C ABI.
+// Shared host-side helpers for the C ABI (and, through device_util.hpp, the device helpers the kernel sources share).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -7,6 +7,7 @@
 #include <map>
 #include <mutex>
 #include <utility>
+#include "device_util.hpp"
 
 namespace mt {
 

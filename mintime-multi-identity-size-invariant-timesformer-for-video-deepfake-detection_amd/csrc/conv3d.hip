@@ -63,9 +63,6 @@ __device__ __forceinline__ void mma_step(const float (*As)[BM + LP], const float
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[2 * kk + h][wm * 32 + r], Bs[2 * kk + h][wn * 32 + r], acc, 0, 0, 0);
 }
 
-// accumulator register i of lane l holds row (i & 3) + 8 (i >> 2) + 4 (l >> 5), column l & 31 of the wavefront's 32 x 32 tile
-__device__ __forceinline__ int acc_row(int i, int lane) { return (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5); }
-
 // ---- forward: M = N*To*Ho*Wo output rows, N = K output channels, reduction over taps * C --------------------------------------
 template <bool PRO>
 __global__ __launch_bounds__(256) void fwd_kernel(Geo g, const float* __restrict__ x, const float* __restrict__ scale,
@@ -104,7 +101,7 @@ __global__ __launch_bounds__(256) void fwd_kernel(Geo g, const float* __restrict
   if (col < g.K) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int64_t row = m0 + wm * 32 + acc_row(i, lane);
+      const int64_t row = m0 + wm * 32 + mfma_slot_row(i, lane >> 5);
       if (row < M) {
         float* p = y + row * g.ldy + col;
         *p = accumulate ? *p + acc[i] : acc[i];
@@ -167,7 +164,7 @@ __global__ __launch_bounds__(256) void dgrad_kernel(Geo g, const float* __restri
   if (col < g.C) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int64_t row = m0 + wm * 32 + acc_row(i, lane);
+      const int64_t row = m0 + wm * 32 + mfma_slot_row(i, lane >> 5);
       if (row < M) {
         float* p = dx + row * g.ldx + col;
         *p = accumulate ? *p + acc[i] : acc[i];
@@ -211,7 +208,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(Geo g, const float* __restri
     float* o = out + (int64_t)blockIdx.z * g.K * KD;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int row = m0 + wm * 32 + acc_row(i, lane);
+      const int row = m0 + wm * 32 + mfma_slot_row(i, lane >> 5);
       if (row < g.K) o[(int64_t)row * KD + col] = acc[i];
     }
   }

@@ -19,32 +19,6 @@ using namespace mt;
 
 namespace {
 
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }   /* v_rcp_f32 (1 ulp) instead of the 10-instruction IEEE division: the swish kernels are VALU-bound */
-__device__ __forceinline__ float swishf_(float x) { return x * sigmoidf_(x); }
-__device__ __forceinline__ float dswishf_(float u) { const float s = sigmoidf_(u); return s * (1.0f + u * (1.0f - s)); }
-
-__device__ __forceinline__ float4 f4(float a, float b, float c, float d) { return make_float4(a, b, c, d); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
-  return f4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
-}
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return f4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return f4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
-template <int ACT>
-__device__ __forceinline__ float4 act4(float4 u) {
-  if (ACT == 1) return f4(swishf_(u.x), swishf_(u.y), swishf_(u.z), swishf_(u.w));
-  if (ACT == 2) return f4(fmaxf(u.x, 0.f), fmaxf(u.y, 0.f), fmaxf(u.z, 0.f), fmaxf(u.w, 0.f));
-  return u;
-}
-template <int ACT>
-__device__ __forceinline__ float4 dact4(float4 u) {     // derivative of the activation at pre-activation u
-  if (ACT == 1) return f4(dswishf_(u.x), dswishf_(u.y), dswishf_(u.z), dswishf_(u.w));
-  if (ACT == 2) return f4(u.x > 0.f ? 1.f : 0.f, u.y > 0.f ? 1.f : 0.f, u.z > 0.f ? 1.f : 0.f, u.w > 0.f ? 1.f : 0.f);
-  return f4(1.f, 1.f, 1.f, 1.f);
-}
-
 // block-level reduction of per-thread (s1,s2) float4 partials over the PB row-lanes, then fp64 atomics
 __device__ __forceinline__ void reduce_stats(float* red, float4 s1, float4 s2, int cql, int pl, int CQB, int PB, int CQ,
                                              int C, double* stats, int slots) {
@@ -198,21 +172,6 @@ __global__ __launch_bounds__(256) void se_bwd_reduce_kernel(const float* __restr
 // (2) one block per (image, 256 channels): sums the slab partials, applies swish', and forms dpooled with four load chains.
 constexpr int SE_SLAB = 128;
 constexpr int SE_JW = 12;            // CS_MAX / 4 squeeze channels per wavefront
-__device__ __forceinline__ void se_load_slab(float* slab, const float* __restrict__ src, int count, int CS, int tid) {
-  const int pitch = CS + 1;
-  const float inv_cs = 1.0f / (float)CS;
-  for (int e0 = tid; e0 < count; e0 += 256 * 8) {                // eight loads in flight per thread, then the LDS writes
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = src[min(e0 + 256 * u, count - 1)];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int e = e0 + 256 * u;
-      const int r = (int)(((float)e + 0.5f) * inv_cs);          // e / CS, exact for e < 2^16
-      if (e < count) slab[r * pitch + (e - r * CS)] = v[u];
-    }
-  }
-}
 
 __global__ __launch_bounds__(256) void se_bwd_slab_kernel(const float* __restrict__ dgate, const float* __restrict__ gate,
                                                           const float* __restrict__ w2, float* __restrict__ dpre2,
@@ -442,7 +401,7 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_tiled_kernel(
       else zraw = pre[i];
       if (pix < IH * IH) {
         const int iy = pix / IH, ix = pix - iy * IH;
-        const float4 v = act4<ACT>(fma4(zraw, sc, sh));
+        const float4 v = act_affine4<ACT>(zraw, sc, sh);
         const bool ok = (pre_ok >> i) & 1u;
         st4(a_t + (iy * IWP + ix) * CC + f_q * 4, f4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f));
       }

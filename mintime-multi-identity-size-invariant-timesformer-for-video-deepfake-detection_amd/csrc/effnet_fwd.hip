@@ -32,16 +32,6 @@ using namespace mt;
 
 namespace {
 
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }   /* v_rcp_f32 (1 ulp) instead of the 10-instruction IEEE division: the swish kernels are VALU-bound */
-__device__ __forceinline__ float swishf_(float x) { return x * sigmoidf_(x); }
-
-__device__ __forceinline__ float4 bn_swish4(float4 z, float4 sc, float4 sh) {
-  float4 a;
-  a.x = swishf_(fmaf(z.x, sc.x, sh.x)); a.y = swishf_(fmaf(z.y, sc.y, sh.y));
-  a.z = swishf_(fmaf(z.z, sc.z, sh.z)); a.w = swishf_(fmaf(z.w, sc.w, sh.w));
-  return a;
-}
-
 __device__ __forceinline__ void atomic_add_f64(double* p, double v) { atomicAdd(p, v); }
 
 // ------------------------------------------------------------------------------------------------ depthwise, LDS-tiled
@@ -49,15 +39,7 @@ __device__ __forceinline__ void atomic_add_f64(double* p, double v) { atomicAdd(
 // once in LDS (swish evaluated once per element, not once per tap); thread (cq = tid&3, slot = tid>>2) then produces the
 // outputs slot, slot+64, ... of the tile for its channel quad with its K*K weights held in registers.  BatchNorm sums
 // stay in registers across the block's tiles -> one fp64 atomic per channel per block.
-template <int ACT>
-__device__ __forceinline__ float4 act_affine4(float4 z, float4 sc, float4 sh) {
-  float4 a = make_float4(fmaf(z.x, sc.x, sh.x), fmaf(z.y, sc.y, sh.y), fmaf(z.z, sc.z, sh.z), fmaf(z.w, sc.w, sh.w));
-  if (ACT == 1) { a.x = swishf_(a.x); a.y = swishf_(a.y); a.z = swishf_(a.z); a.w = swishf_(a.w); }
-  if (ACT == 2) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
-  return a;
-}
-
-// ACT: input activation applied after the per-channel affine (0 none, 1 swish [EfficientNet], 2 relu [Xception]).
+// ACT: input activation applied after the per-channel affine (act_affine4: 0 none, 1 swish [EfficientNet], 2 relu [Xception]).
 // CC : channels per block (16, or 8 for channel counts like Xception's 728 that are not multiples of 16).
 // RC : 0 = zin is the conv's raw input [N,H,W,C]; Cin > 0 = zin is the BLOCK input y [N,H,W,Cin] and the raw input chunk is rebuilt
 //      as y . We^T while the tile is staged (rc.hpp; we = the expand weight [C, Cin]) -- the expanded tensor is not read.
@@ -318,12 +300,12 @@ __global__ __launch_bounds__(256) void se_pool_kernel(const float* __restrict__ 
       const float4 v1 = *reinterpret_cast<const float4*>(base + (int64_t)(p + PB) * C);
       const float4 v2 = *reinterpret_cast<const float4*>(base + (int64_t)(p + 2 * PB) * C);
       const float4 v3 = *reinterpret_cast<const float4*>(base + (int64_t)(p + 3 * PB) * C);
-      const float4 a0 = bn_swish4(v0, sc, sh), a1 = bn_swish4(v1, sc, sh), a2 = bn_swish4(v2, sc, sh), a3 = bn_swish4(v3, sc, sh);
+      const float4 a0 = act_affine4<1>(v0, sc, sh), a1 = act_affine4<1>(v1, sc, sh), a2 = act_affine4<1>(v2, sc, sh), a3 = act_affine4<1>(v3, sc, sh);
       s.x += (a0.x + a1.x) + (a2.x + a3.x); s.y += (a0.y + a1.y) + (a2.y + a3.y);
       s.z += (a0.z + a1.z) + (a2.z + a3.z); s.w += (a0.w + a1.w) + (a2.w + a3.w);
     }
     for (; p < p_hi; p += PB) {
-      const float4 a = bn_swish4(*reinterpret_cast<const float4*>(base + (int64_t)p * C), sc, sh);
+      const float4 a = act_affine4<1>(*reinterpret_cast<const float4*>(base + (int64_t)p * C), sc, sh);
       s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
     }
   }
@@ -381,23 +363,6 @@ __global__ __launch_bounds__(256) void se_hidden_kernel(const float* __restrict_
   if (lane < 4 && j0 + lane < CS) {
     const float a = lane == 0 ? a0 : (lane == 1 ? a1 : (lane == 2 ? a2 : a3));
     hidden[(int64_t)n * CS + j0 + lane] = a + b1[j0 + lane];
-  }
-}
-
-// loads `count` consecutive floats of src into the [rows][CS+1] slab image, eight loads in flight per thread
-__device__ __forceinline__ void se_load_slab(float* slab, const float* __restrict__ src, int count, int CS, int tid) {
-  const int pitch = CS + 1;
-  const float inv_cs = 1.0f / (float)CS;
-  for (int e0 = tid; e0 < count; e0 += 256 * 8) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = src[min(e0 + 256 * u, count - 1)];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int e = e0 + 256 * u;
-      const int r = (int)(((float)e + 0.5f) * inv_cs);          // e / CS, exact for e < 2^16
-      if (e < count) slab[r * pitch + (e - r * CS)] = v[u];
-    }
   }
 }
 

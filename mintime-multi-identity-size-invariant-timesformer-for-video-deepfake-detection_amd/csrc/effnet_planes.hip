@@ -19,9 +19,6 @@ using namespace mt;
 
 namespace {
 
-__device__ __forceinline__ float sigmoid_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }   /* v_rcp_f32 (1 ulp) instead of the 10-instruction IEEE division: the swish kernels are VALU-bound */
-__device__ __forceinline__ float swish_(float x) { return x * sigmoid_(x); }      // (the formula of effnet_fwd.hip / gemm_core.hpp)
-
 __global__ __launch_bounds__(256) void bn_act_planes_kernel(const float* __restrict__ z, const float* __restrict__ scale,
                                                             const float* __restrict__ shift, const float* __restrict__ res,
                                                             float* __restrict__ y, int R, int C, int act,
@@ -42,7 +39,7 @@ __global__ __launch_bounds__(256) void bn_act_planes_kernel(const float* __restr
         float t[4] = {fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w)};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          if (act == 1) t[q] = swish_(t[q]);
+          if (act == 1) t[q] = swishf_(t[q]);
           else if (act == 2) t[q] = fmaxf(t[q], 0.f);
           if (rowscale) t[q] *= g;                       // (same operation order as bn_act_kernel: the two agree to the bit)
         }
@@ -80,7 +77,7 @@ __global__ __launch_bounds__(256) void bn_act_planes_rows_kernel(const float* __
       const float g = rowscale ? rowscale[r / rows_per_group] : 1.f;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        if (act == 1) t[q] = swish_(t[q]);
+        if (act == 1) t[q] = swishf_(t[q]);
         else if (act == 2) t[q] = fmaxf(t[q], 0.f);
         if (rowscale) t[q] *= g;
       }
@@ -121,8 +118,8 @@ __global__ __launch_bounds__(256) void bn_swish_gate_planes_kernel(const float* 
         const float4 sc = *reinterpret_cast<const float4*>(scale + c + e), sh = *reinterpret_cast<const float4*>(shift + c + e);
         const float4 g = *reinterpret_cast<const float4*>(grow + c + e);
         // the project convolution's operand as mt_gemm's PRO_BN_SWISH_GATE prologue forms it: swish(z * scale + shift) * gate
-        x[e] = swish_(fmaf(v.x, sc.x, sh.x)) * g.x; x[e + 1] = swish_(fmaf(v.y, sc.y, sh.y)) * g.y;
-        x[e + 2] = swish_(fmaf(v.z, sc.z, sh.z)) * g.z; x[e + 3] = swish_(fmaf(v.w, sc.w, sh.w)) * g.w;
+        x[e] = swishf_(fmaf(v.x, sc.x, sh.x)) * g.x; x[e + 1] = swishf_(fmaf(v.y, sc.y, sh.y)) * g.y;
+        x[e + 2] = swishf_(fmaf(v.z, sc.z, sh.z)) * g.z; x[e + 3] = swishf_(fmaf(v.w, sc.w, sh.w)) * g.w;
       }
     }
   }

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "common.hpp"
+#include "device_util.hpp"
 #include "det.hpp"
 
 #ifndef MT_BK
@@ -168,9 +169,7 @@ struct GemmArgs {
   int xcd_k;                            // split-K weight gradients: every XCD owns whole K-ranges (gemm_split.hpp), grid = (tiles, splits % 8 == 0)
 };
 
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }   /* v_rcp_f32 (1 ulp) instead of the 10-instruction IEEE division: the swish kernels are VALU-bound */
-__device__ __forceinline__ float swishf_(float x) { return x * sigmoidf_(x); }
-__device__ __forceinline__ float dswish_gemm_(float u) { const float s = sigmoidf_(u); return s * (1.0f + u * (1.0f - s)); }
+// (sigmoidf_ / swishf_ / dswishf_: device_util.hpp)
 // erf via Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7, i.e. fp32 rounding level) -- libm's erff costs ~3x the VALU slots,
 // and the GEGLU epilogues evaluate it 64x per lane while no MFMA of that wave is in flight.
 __device__ __forceinline__ float erf_fast(float x) {
@@ -326,7 +325,7 @@ __device__ __forceinline__ void gemm_epilogue_body(const GemmArgs& p, f32x16 (&a
             if constexpr (EPI == EPI_SE_RED) {
               run = fmaf(acc[i][j][r], swishf_(u), run);
             } else {
-              const float d = fmaf(acc[i][j][r], g, dp) * dswish_gemm_(u);
+              const float d = fmaf(acc[i][j][r], g, dp) * dswishf_(u);
               cp[(int64_t)dr * p.ldc] = d;
               s1 += d;
               s2 = fmaf(d, (z - mean) * istd, s2);

@@ -33,8 +33,6 @@ struct ConvArgs {
   int64_t rows; int Cin, Cout, hw;
 };
 
-__device__ __forceinline__ float swish_f(float v) { return v * __builtin_amdgcn_rcpf(1.f + __expf(-v)); }   /* v_rcp_f32 (1 ulp), see effnet_fwd.hip sigmoidf_ */
-
 // KT = 32-wide k tiles (Cin <= 32 KT), NT = 32-wide output column tiles, R = rows per chunk (one 32-row tile per wavefront at
 // R = 128, two wavefronts per row tile at R = 64)
 template <int KT, int NT, int R, int AMODE>
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(256) void conv1x1_rows_kernel(ConvArgs p) {
           const float4 g = *reinterpret_cast<const float4*>(p.gate + img * p.Cin + ac[i]);
           const float gg[4] = {g.x, g.y, g.z, g.w};
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = swish_f(fmaf(cst[ac[i] + e], v[e], cst[KT * 32 + ac[i] + e])) * gg[e];
+          for (int e = 0; e < 4; ++e) v[e] = swishf_(fmaf(cst[ac[i] + e], v[e], cst[KT * 32 + ac[i] + e])) * gg[e];
         }
       } else if constexpr (AMODE == A_BNBWD) {
         const float z[4] = {rx2[i].x, rx2[i].y, rx2[i].z, rx2[i].w};

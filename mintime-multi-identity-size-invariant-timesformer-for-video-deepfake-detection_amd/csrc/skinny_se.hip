@@ -33,8 +33,6 @@ struct SeArgs {
   int64_t rows; int Co, C, hw;
 };
 
-__device__ __forceinline__ float sigmoid_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }   /* v_rcp_f32 (1 ulp) instead of the 10-instruction IEEE division: the swish kernels are VALU-bound */
-
 enum { MODE_RED = 0, MODE_ACT = 1 };
 
 // NT = 32-wide tiles of C (1, 3, 5), CQB = C / 4 (8, 24, 36).  Thread (cql, pl): column quad cql, row lane pl of the PB = 256 / CQB lanes.
@@ -183,7 +181,7 @@ __global__ __launch_bounds__(256) void se_stage_kernel(SeArgs p) {
           const float4 a = *reinterpret_cast<const float4*>(das + row * LDA + c4);
           const float4 zz = rzd[i];
           const float ux = fmaf(zz.x, sc.x, sh.x), uy = fmaf(zz.y, sc.y, sh.y), uz = fmaf(zz.z, sc.z, sh.z), uw = fmaf(zz.w, sc.w, sh.w);
-          const float sx = sigmoid_(ux), sy = sigmoid_(uy), sz = sigmoid_(uz), sw = sigmoid_(uw);
+          const float sx = sigmoidf_(ux), sy = sigmoidf_(uy), sz = sigmoidf_(uz), sw = sigmoidf_(uw);
           if (MODE == MODE_RED) {
             s1.x = fmaf(a.x, ux * sx, s1.x); s1.y = fmaf(a.y, uy * sy, s1.y); s1.z = fmaf(a.z, uz * sz, s1.z); s1.w = fmaf(a.w, uw * sw, s1.w);
           } else {

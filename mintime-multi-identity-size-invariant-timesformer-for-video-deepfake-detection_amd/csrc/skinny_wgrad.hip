@@ -33,7 +33,6 @@ struct WgradArgs {
 
 enum { A_PLAIN = 0, A_GATE = 1, A_STEM = 2 };
 
-__device__ __forceinline__ float swish_f(float v) { return v * __builtin_amdgcn_rcpf(1.f + __expf(-v)); }   /* v_rcp_f32 (1 ulp), see effnet_fwd.hip sigmoidf_ */
 // component-wise on purpose: `c ? a : zero4` on the structs makes the compiler select between two stack slots
 __device__ __forceinline__ float4 keep_if(bool c, const float4& a) { return make_float4(c ? a.x : 0.f, c ? a.y : 0.f, c ? a.z : 0.f, c ? a.w : 0.f); }
 
@@ -184,10 +183,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const float4 s = *reinterpret_cast<const float4*>(ssh + ac[i]);
             const float4 h = *reinterpret_cast<const float4*>(ssh + NT * 32 + ac[i]);
             const float4 g = *reinterpret_cast<const float4*>(p.gate + img * p.Cin + ac[i]);
-            v.x = swish_f(fmaf(s.x, v.x, h.x)) * g.x;
-            v.y = swish_f(fmaf(s.y, v.y, h.y)) * g.y;
-            v.z = swish_f(fmaf(s.z, v.z, h.z)) * g.z;
-            v.w = swish_f(fmaf(s.w, v.w, h.w)) * g.w;
+            v.x = swishf_(fmaf(s.x, v.x, h.x)) * g.x;
+            v.y = swishf_(fmaf(s.y, v.y, h.y)) * g.y;
+            v.z = swishf_(fmaf(s.z, v.z, h.z)) * g.z;
+            v.w = swishf_(fmaf(s.w, v.w, h.w)) * g.w;
           }
           *reinterpret_cast<float4*>(as + ar[i] * LDA + ac[i]) = v;
         }

@@ -14,12 +14,6 @@ int64_t colsum_mid_floats(int64_t rows, int cols);
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ---- BatchNorm + ReLU (+ residual) ----------------------------------------------------------------------------------------------
 // y = relu(z * scale + shift + r), r = res * rscale + rshift (rscale given: the shortcut's own BatchNorm), res (identity), or 0
 __global__ __launch_bounds__(256) void bn_relu_fwd_kernel(const float* __restrict__ z, int64_t ldz, const float* __restrict__ scale,

@@ -21,17 +21,6 @@ namespace {
 
 constexpr int DH = 64;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------- LayerNorm backward
 // one wavefront per row, grid-strided so each wave keeps dgamma/dbeta partials in registers.  NI = float4 slots per lane
 // (ceil(D / 256)): sized to the row width, the register arrays cost 100 instead of 200 VGPRs at D = 512, which lets these
@@ -666,17 +655,6 @@ __global__ __launch_bounds__(256) void embed_bwd_limb_decode_kernel(const double
 #endif
 constexpr int CLS_W = MT_CLS_W;          // (16 wavefronts: the N keys in two trips of 256 -- with 4 the kernel was a chain of 2 x 7 exposed round trips)
 
-__device__ __forceinline__ float block_reduce(float v, float* red, int wave, int lane, bool is_max) {
-  v = is_max ? wave_max(v) : wave_sum(v);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = red[0];
-#pragma unroll
-  for (int w = 1; w < CLS_W; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  return r;
-}
-
 // The "factored" hand-over of the cls query's contribution to the patch keys (plane output only): per key and head the two scalars
 // dS_j and p_j of dk_j += dS_j (s q_cls), dv_j += p_j dO_cls -- the kernel that owns the key forms the rank-1 terms itself.  They live
 // in a part of the fp32 dqkv working buffer nothing else uses with plane output: the q-section (columns [0, inner)) of the clip's patch
@@ -741,14 +719,14 @@ __global__ __launch_bounds__(CLS_W * 64) void attn_cls_bwd_kernel(const float* _
   __syncthreads();
   float mx = -FLT_MAX;
   for (int j = tid; j < N; j += CLS_W * 64) mx = fmaxf(mx, pl_[j]);
-  mx = block_reduce(mx, red, wave, lane, true);
+  mx = block_reduce<CLS_W>(mx, red, wave, lane, true);
   float sum = 0.f;
   for (int j = tid; j < N; j += CLS_W * 64) { const float e = expf(pl_[j] - mx); pl_[j] = e; sum += e; }
-  sum = block_reduce(sum, red, wave, lane, false);
+  sum = block_reduce<CLS_W>(sum, red, wave, lane, false);
   const float inv = 1.0f / sum;
   float delta = 0.f;
   for (int j = tid; j < N; j += CLS_W * 64) { const float p = pl_[j] * inv; pl_[j] = p; delta += p * ds_[j]; }
-  delta = block_reduce(delta, red, wave, lane, false);
+  delta = block_reduce<CLS_W>(delta, red, wave, lane, false);
   __syncthreads();
   // per key: dS; dk_j = dS * q_scaled, dv_j = p * dO (stores), dq += dS * k_j
   float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -805,8 +783,6 @@ __global__ __launch_bounds__(CLS_W * 64) void attn_cls_bwd_kernel(const float* _
 // 896 v_mfma_f32_32x32x2_f32 per group.  dq is stored; dk / dv are added onto the cls query's contribution written by
 // attn_cls_bwd_kernel (read-modify-write: a patch key belongs to exactly one group; fp32 atomics for the shared cls key).
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int mfma_slot_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
 
 __device__ __forceinline__ void load_row32(const float* __restrict__ p, float (&dst)[32], float mul) {
 #pragma unroll

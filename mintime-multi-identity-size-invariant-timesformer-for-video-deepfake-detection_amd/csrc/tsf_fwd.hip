@@ -26,17 +26,6 @@ namespace {
 
 constexpr int DH = 64;   // dim_head (config: dim-head 64)
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------- LayerNorm
 // one wavefront per row; D % 4 == 0, D <= 1024
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -386,8 +375,6 @@ __global__ __launch_bounds__(WPB * 64, F == 8 ? 4 : 2) void attn_time_fwd_kernel
 // 256 v_mfma_f32_32x32x2_f32 per group against ~100 k VALU FMAs + 100 LDS reads per lane in the one-lane-per-query kernel.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ int mfma_slot_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
-
 template <int WPB>
 __global__ __launch_bounds__(WPB * 64) void attn_space_fwd_mfma_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                       int B, int H, int F, int n, float scale, const PlaneRef op) {
@@ -507,17 +494,6 @@ __global__ __launch_bounds__(WPB * 64) void attn_space_fwd_mfma_kernel(const flo
 #endif
 constexpr int CLS_W = MT_CLS_W;          // (16 wavefronts: the N keys in two trips of 256 -- with 4 the kernel was a chain of 2 x 7 exposed round trips)
 
-__device__ __forceinline__ float block_reduce(float v, float* red, int wave, int lane, bool is_max) {
-  v = is_max ? wave_max(v) : wave_sum(v);
-  __syncthreads();                                   // red may still be read from the previous reduction
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = red[0];
-#pragma unroll
-  for (int w = 1; w < CLS_W; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  return r;
-}
-
 // Lane mapping: 16 lanes per key (lane & 15 = which float4 of the 64-wide head), 16 keys per pass: every K / V row is one coalesced
 // 256-byte access.  All reductions have a fixed order (eval stays bit-reproducible).
 __global__ __launch_bounds__(CLS_W * 64) void attn_cls_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
@@ -556,10 +532,10 @@ __global__ __launch_bounds__(CLS_W * 64) void attn_cls_fwd_kernel(const float* _
   __syncthreads();
   float mx = -FLT_MAX;
   for (int j = tid; j < N; j += CLS_W * 64) mx = fmaxf(mx, lds[j]);
-  mx = block_reduce(mx, red, wave, lane, true);
+  mx = block_reduce<CLS_W>(mx, red, wave, lane, true);
   float sum = 0.f;
   for (int j = tid; j < N; j += CLS_W * 64) { const float e = expf(lds[j] - mx); lds[j] = e; sum += e; }
-  sum = block_reduce(sum, red, wave, lane, false);
+  sum = block_reduce<CLS_W>(sum, red, wave, lane, false);
   const float inv = 1.0f / sum;
   for (int j = tid; j < N; j += CLS_W * 64) {
     const float pj = lds[j] * inv;

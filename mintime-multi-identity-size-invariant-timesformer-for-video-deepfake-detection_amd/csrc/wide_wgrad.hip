@@ -34,8 +34,6 @@ struct WideArgs {
   int nslab, nsplit; int64_t chunks_per_split;
 };
 
-__device__ __forceinline__ float swish_w(float v) { return v * __builtin_amdgcn_rcpf(1.f + __expf(-v)); }   /* v_rcp_f32 (1 ulp), see effnet_fwd.hip sigmoidf_ */
-
 constexpr int R = 32;                      // rows per chunk
 constexpr int SLAB = 128;                  // columns of C per block
 constexpr int LDA = SLAB + 32;             // pitch % 64 == 32: the two k-rows of a fragment read hit disjoint banks
@@ -148,10 +146,10 @@ __global__ __launch_bounds__(512) void wgrad_wide_kernel(WideArgs p) {
         const bool ok = a_on && row < left;
         const float4 v = rx[SET][i], g = rg[SET][i];
         float4 o;
-        o.x = ok ? swish_w(fmaf(s4.x, v.x, h4.x)) * g.x : 0.f;
-        o.y = ok ? swish_w(fmaf(s4.y, v.y, h4.y)) * g.y : 0.f;
-        o.z = ok ? swish_w(fmaf(s4.z, v.z, h4.z)) * g.z : 0.f;
-        o.w = ok ? swish_w(fmaf(s4.w, v.w, h4.w)) * g.w : 0.f;
+        o.x = ok ? swishf_(fmaf(s4.x, v.x, h4.x)) * g.x : 0.f;
+        o.y = ok ? swishf_(fmaf(s4.y, v.y, h4.y)) * g.y : 0.f;
+        o.z = ok ? swishf_(fmaf(s4.z, v.z, h4.z)) * g.z : 0.f;
+        o.w = ok ? swishf_(fmaf(s4.w, v.w, h4.w)) * g.w : 0.f;
         *reinterpret_cast<float4*>(ab + row * LDA + ac) = o;
       }
     };

@@ -4,6 +4,7 @@ import torch
 from . import arch
 from . import lib as L
 from .effnet_engine import SLOTS, STREAM_ROWS, _StatsPool
+from .lib import _new
 
 
 # Depthwise data AND weight gradient from one pass over du / z / the depthwise input (csrc/effnet_bwd.hip, WG = true): the gather leaves
@@ -23,10 +24,6 @@ WIDE_WGRAD = __import__("os").environ.get("MT_WIDE_WGRAD", "1") != "0"      # la
 # squeeze-excite reverse stage of the early blocks (stages 0-2) as two STREAMING passes that rebuild the project conv's data gradient
 # from the narrow gradient (skinny_se.hip): 3 instead of 6 passes over the expanded tensor, no da tensor
 SE_STREAM = __import__("os").environ.get("MT_SE_STREAM", "1") != "0"     # expand-conv data + weight gradient in one pass (stages 1-3)
-
-
-def _new(dev, *shape):
-    return torch.empty(*shape, dtype=torch.float32, device=dev)
 
 
 def _splits(rows):

@@ -7,6 +7,7 @@ import torch
 from . import arch
 from . import lib as L
 from . import plans
+from .lib import _new
 
 SLOTS = 32   # replicated fp64 BatchNorm accumulators (spreads atomic traffic)
 STEM_DIRECT = __import__("os").environ.get("MT_STEM_DIRECT", "1") != "0"    # 0 = the im2col-prologue GEMM
@@ -25,10 +26,6 @@ EF_RC_MIN_ROWS = int(__import__("os").environ.get("MT_EF_RC_ROWS", "100000"))   
 EF_PLANES = __import__("os").environ.get("MT_EF_PLANES", "1") != "0"
 EF_PLANES_EXPAND_HW = int(__import__("os").environ.get("MT_EF_PLANES_EXPAND_HW", "14"))
 EF_PLANES_PROJECT_HW = int(__import__("os").environ.get("MT_EF_PLANES_PROJECT_HW", "7"))
-
-
-def _new(dev, *shape):
-    return torch.empty(*shape, dtype=torch.float32, device=dev)
 
 
 def param_list(model):
@@ -70,11 +67,13 @@ class _StatsPool:
         return v
 
 
-def _finalize(lib, st, bn_mod, ctx, count, training, gamma, beta, slots=SLOTS):
+def _finalize(lib, bn_mod, ctx, count, training, gamma, beta, slots=SLOTS, st=None):
+    """slots < 0 (deterministic mode): the producers' statistics are integer limbs (csrc/common.hpp stat_add, _StatsPool).
+    st: the stream to launch on (default: the current stream)."""
     ctx.count = float(count)
     L.check(lib.mt_bn_finalize(L.ptr(ctx.stats), slots, float(count), L.ptr(gamma), L.ptr(beta), L.ptr(bn_mod.running_mean),
                                L.ptr(bn_mod.running_var), L.ptr(ctx.scale), L.ptr(ctx.shift), L.ptr(ctx.mean_invstd), ctx.C,
-                               bn_mod.eps, bn_mod.momentum, 1 if training else 0, st), "mt_bn_finalize")
+                               bn_mod.eps, bn_mod.momentum, 1 if training else 0, L.stream_ptr() if st is None else st), "mt_bn_finalize")
     if training:
         _track(bn_mod.num_batches_tracked)
 
@@ -213,7 +212,7 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
         L.check(lib.mt_conv_weight_pack(L.ptr(w_stem), L.ptr(wp), arch.STEM_COUT, 3, 3, 28, 0, st), "mt_conv_weight_pack")
         L.gemm(L.OP_NT, x_nhwc, wp, z, N * Hc * Wc, arch.STEM_COUT, 28, 28, 28, arch.STEM_COUT, prologue=L.PRO_IM2COL, epilogue=epi,
                stats=bn.stats, stats_slots=slots, conv=(H, W, 3, Hc, Wc, 3, 2, 0, 0, 1 if x_nhwc.dtype == torch.uint8 else 0))
-    _finalize(lib, st, model._bn0, bn, N * Hc * Wc, training, g0, b0, slots)
+    _finalize(lib, model._bn0, bn, N * Hc * Wc, training, g0, b0, slots, st)
     if save:
         saved["stem"] = dict(x=x_nhwc, z=z, bn=bn)
     cur_z, cur_bn = z, bn        # "virtual" activated tensor: swish(bn(z))
@@ -249,7 +248,7 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
                                             sptr(bn_e), slots, M_in, s.cin, s.cexp, st), "mt_conv1x1_rows")
             else:
                 L.gemm(L.OP_NT, y, w_e, z_e, M_in, s.cexp, s.cin, s.cin, s.cin, s.cexp, epilogue=epi, stats=bn_e.stats, stats_slots=slots)
-            _finalize(lib, st, blk._bn0, bn_e, M_in, training, g, b, slots)
+            _finalize(lib, blk._bn0, bn_e, M_in, training, g, b, slots, st)
             rec.update(z_e=z_e, bn_e=bn_e, rc=rc_on, w_e=w_e)
             dw_in, dw_bn = z_e, bn_e
         else:
@@ -264,7 +263,7 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
         else:
             L.check(lib.mt_dwconv_fwd(L.ptr(dw_in), L.ptr(dw_bn.scale), L.ptr(dw_bn.shift), L.ptr(w_d), L.ptr(z_d), sptr(bn_d),
                                       slots, N, s.hin, s.hin, s.cexp, s.k, s.s, 1, st), "mt_dwconv_fwd")
-        _finalize(lib, st, blk._bn1, bn_d, M_out, training, g, b, slots)
+        _finalize(lib, blk._bn1, bn_d, M_out, training, g, b, slots, st)
         w_r, b_r, w_x, b_x = next(it), next(it), next(it), next(it)
         pooled, gate = _new(dev, N, s.cexp), _new(dev, N, s.cexp)
         hidden = _new(dev, N, s.cse)          # squeeze pre-activations: the gate kernel reads them (and backward keeps them)
@@ -292,7 +291,7 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
         else:
             L.gemm(L.OP_NT, z_d, w_p, z_p, M_out, s.cout, s.cexp, s.cexp, s.cexp, s.cout, prologue=L.PRO_BN_SWISH_GATE, epilogue=epi,
                    scale=bn_d.scale, shift=bn_d.shift, gate=gate, hw=hw, stats=bn_p.stats, stats_slots=slots)
-        _finalize(lib, st, blk._bn2, bn_p, M_out, training, g, b, slots)
+        _finalize(lib, blk._bn2, bn_p, M_out, training, g, b, slots, st)
         # block output: bn2(z_p) [* drop-connect gate] [+ block input]
         dc = dc_gates.get(bi)
         y_new = _new(dev, M_out, s.cout)
@@ -325,7 +324,7 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
     else:
         L.gemm(L.OP_NT, y, w_h, z_h, M, arch.HEAD_COUT, arch.HEAD_CIN, arch.HEAD_CIN, arch.HEAD_CIN, arch.HEAD_COUT, epilogue=epi,
                stats=bn_h.stats, stats_slots=slots)
-    _finalize(lib, st, model._bn1, bn_h, M, training, g, b, slots)
+    _finalize(lib, model._bn1, bn_h, M, training, g, b, slots, st)
     feat = _new(dev, M, arch.HEAD_COUT)
     L.check(lib.mt_bn_act_fwd(L.ptr(z_h), L.ptr(bn_h.scale), L.ptr(bn_h.shift), None, L.ptr(feat), M, arch.HEAD_COUT, 1, None, 1,
                               st), "mt_bn_act_fwd")

@@ -496,6 +496,11 @@ def tag_next(tag, work=0.0):
         get().mt_plan_tag(tag, float(work))
 
 
+def _new(dev, *shape):
+    """The engines' fp32 scratch / output tensor, uninitialised."""
+    return torch.empty(*shape, dtype=torch.float32, device=dev)
+
+
 def zeros(shape, dtype, device):
     """torch.zeros as torch.empty + mt_memset_async: the fill is an entry point of the library, so a recorded phase re-issues it."""
     if torch.device(device).type != "cuda":

@@ -14,6 +14,7 @@ import torch
 from . import arch
 from . import lib as L
 from . import plans, tsf_planes
+from .lib import _new
 from .tsf_backward import tsf_backward
 
 
@@ -92,10 +93,6 @@ def _publish_index_flag(state):
     ev = torch.cuda.Event()
     ev.record()
     state[2] = ev
-
-
-def _new(dev, *shape):
-    return torch.empty(*shape, dtype=torch.float32, device=dev)
 
 
 def tsf_forward(model, feat, aux, params, B, F, n, save):

@@ -22,6 +22,7 @@ import torch
 from . import arch
 from . import lib as L
 from . import plans
+from .lib import _new
 
 # LayerNorm backward: parameter-gradient column sums folded into the rows kernel as per-block partials (MT_LN_FOLD=0: the second pass
 # over dy / x / dx on the weight-gradient stream)
@@ -83,10 +84,6 @@ def weight_planes(model, params, training):
         L.check(lib.mt_split_planes_blk_multi(L.ptr(cache["table"]), cache["count"], cache["blocks"], L.stream_ptr()),
                 "mt_split_planes_blk_multi")         # (L.ptr: a launch plan being recorded pins the table)
     return cache["holder"], cache["serial"].touch(ws)
-
-
-def _new(dev, *shape):
-    return torch.empty(*shape, dtype=torch.float32, device=dev)
 
 
 def tsf_forward_planes(model, feat, aux, params, B, F, n, save):

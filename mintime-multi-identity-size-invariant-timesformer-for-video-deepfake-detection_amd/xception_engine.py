@@ -9,7 +9,8 @@ import torch
 from . import arch
 from . import lib as L
 from . import plans
-from .effnet_engine import SLOTS, _StatsPool, _BNCtx, _track, _bump_tracked
+from .effnet_engine import SLOTS, _StatsPool, _BNCtx, _finalize, _bump_tracked
+from .lib import _new
 
 RELU, NONE = 2, 0
 
@@ -22,10 +23,6 @@ CONV2_WGRAD_SIDE = float(__import__("os").environ.get("MT_XC_CONV2_WGRAD_SIDE", 
 XC_STEM = __import__("os").environ.get("MT_XC_STEM", "1") != "0"             # 0: conv1 as an im2col GEMM (round 4)
 SKIP_HALF = __import__("os").environ.get("MT_XC_SKIP_HALF", "1") != "0"    # 0: the skip path's data gradient scattered into a zeroed full-size tensor
 POOL_ARG = __import__("os").environ.get("MT_XC_POOL_ARG", "1") != "0"      # 0: the adjoint of the max-pool as an arg-max scatter (round 4)
-
-
-def _new(dev, *shape):
-    return torch.empty(*shape, dtype=torch.float32, device=dev)
 
 
 class _Src:
@@ -73,16 +70,6 @@ def _total_channels(model):
             c += blk.cfg[2]
         c += sum(co for (_, _, _, co) in blk.unit_index)
     return c
-
-
-def _finalize(lib, bn_mod, ctx, count, training, gamma, beta, slots=SLOTS):
-    """slots < 0 (deterministic mode): the producers' statistics are integer limbs (csrc/common.hpp stat_add, effnet_engine._StatsPool)."""
-    ctx.count = float(count)
-    L.check(lib.mt_bn_finalize(L.ptr(ctx.stats), slots, float(count), L.ptr(gamma), L.ptr(beta), L.ptr(bn_mod.running_mean),
-                               L.ptr(bn_mod.running_var), L.ptr(ctx.scale), L.ptr(ctx.shift), L.ptr(ctx.mean_invstd), ctx.C,
-                               bn_mod.eps, bn_mod.momentum, 1 if training else 0, L.stream_ptr()), "mt_bn_finalize")
-    if training:
-        _track(bn_mod.num_batches_tracked)
 
 
 class _WeightPlanes:

@@ -1,6 +1,5 @@
 """Host side of the input-crop gradient: the two stem data-gradient entry points are declared and bound, the ABI number did not move
 (added entry points are backward compatible), and harness.input_gradient refuses what has no gradient before touching a device."""
-import os
 import re
 
 import pytest
@@ -9,27 +8,20 @@ import torch
 import mintime_amd
 from mintime_amd import harness
 from mintime_amd import lib as L
+from tests.util import declared_params, header_text
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("mt_stem_conv_dgrad", "mt_stem_conv_dgrad_valid")
-
-
-def _header():
-    with open(os.path.join(ROOT, "include", "mintime_hip.h")) as f:
-        return f.read()
 
 
 @pytest.mark.parametrize("name", SYMBOLS)
 def test_entry_point_is_declared_and_bound(name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\)\s*;", _header(), flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/mintime_hip.h"
-    params = [p.strip() for p in " ".join(m.group(1).split()).split(",")]
+    params = declared_params(name)
     assert params[-1] == "void* stream"                          # a launching entry point: csrc/gen_plan.py gives it a recording thunk
     assert name in L.PROTOTYPES and len(L.PROTOTYPES[name]) == len(params) == 9
 
 
 def test_abi_version_did_not_move():
-    assert L.ABI_VERSION == 122 and int(re.search(r"#define\s+MT_VERSION\s+(\d+)", _header()).group(1)) == 122
+    assert L.ABI_VERSION == 122 and int(re.search(r"#define\s+MT_VERSION\s+(\d+)", header_text()).group(1)) == 122
 
 
 class _NeverCalled(torch.nn.Module):

@@ -1,7 +1,5 @@
 """Host side of SlowFast's input-clip gradient: the inverse frame map of the ingest's adjoint, the two new entry points' declarations
 and bindings, and the refusals of harness.slowfast_input_gradient / harness.input_gradient before anything touches a device."""
-import os
-import re
 
 import pytest
 import torch
@@ -10,10 +8,9 @@ import mintime_amd
 from mintime_amd import harness
 from mintime_amd import lib as L
 from mintime_amd import slowfast as S
+from tests.util import declared_params
 
 frame_sources = S.frame_sources             # the module needs the feature: without it nothing here is collected
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _check_sources(fidx, F):
@@ -49,11 +46,7 @@ def test_frame_sources_of_the_slow_selection_and_of_both_pathways():
 
 @pytest.mark.parametrize("name,nparams", [("mt_sf_stem_dgrad", 11), ("mt_sf_ingest_bwd", 18)])
 def test_entry_point_is_declared_and_bound(name, nparams):
-    with open(os.path.join(ROOT, "include", "mintime_hip.h")) as f:
-        header = f.read()
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\)\s*;", header, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/mintime_hip.h"
-    params = [p.strip() for p in " ".join(m.group(1).split()).split(",")]
+    params = declared_params(name)
     assert params[-1] == "void* stream"                          # a launching entry point: csrc/gen_plan.py gives it a recording thunk
     assert name in L.PROTOTYPES and len(L.PROTOTYPES[name]) == len(params) == nparams
     assert L.ABI_VERSION == 122                                  # added entry points do not move the ABI number

@@ -1,7 +1,6 @@
 """Host side of the SlowFast input transform's ShortSideScale + CenterCropVideo (interpolation="bilinear"): the size and crop rules,
 the per-axis tap tables and their inverse, the refusals that need no device, and the two entry points' declarations and bindings."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,8 +12,7 @@ from mintime_amd import lib as L
 from mintime_amd import slowfast as S
 
 from . import sf_resize_ref as RR
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from .util import declared_params
 
 # (H, W, side, crop) -> (Hr, Wr), (top, left)
 GEOMETRY = [
@@ -113,11 +111,7 @@ def test_the_default_still_refuses_other_sizes():
 
 @pytest.mark.parametrize("name,nparams", [("mt_sf_ingest_resize", 27), ("mt_sf_ingest_resize_bwd", 30)])
 def test_entry_point_is_declared_and_bound(name, nparams):
-    with open(os.path.join(ROOT, "include", "mintime_hip.h")) as f:
-        header = f.read()
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\)\s*;", header, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/mintime_hip.h"
-    params = [p.strip() for p in " ".join(m.group(1).split()).split(",")]
+    params = declared_params(name)
     assert params[-1] == "void* stream"                          # a launching entry point: csrc/gen_plan.py gives it a recording thunk
     assert name in L.PROTOTYPES and len(L.PROTOTYPES[name]) == len(params) == nparams
     assert os.path.exists(os.path.join(L.CSRC, "sf_resize.hip"))

@@ -1,10 +1,24 @@
 """Shared helpers for the parity tests."""
 import os
+import re
 
 import numpy as np
 import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mintime_hip.h")
+
+
+def header_text():
+    with open(HEADER) as f:
+        return f.read()
+
+
+def declared_params(name):
+    """The parameter list (one "type name" string each) of the entry point `int name(...)` as include/mintime_hip.h declares it."""
+    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\)\s*;", header_text(), flags=re.M | re.S)
+    assert m, f"{name} is not declared in include/mintime_hip.h"
+    return [p.strip() for p in " ".join(m.group(1).split()).split(",")]
 
 # north_star tolerance: outputs within 1e-3 relative, fp32.
 REL_TOL = 1e-3
