@@ -236,7 +236,9 @@ int mt_embed_fwd(float* x, const float* cls, const float* pos_emb, const float* 
  * afterwards -- the optional dead-row pruning of tsf_engine.py; mt_attn_bwd mode 2 is its adjoint: dk / dv of all keys, dq of row 0).
  * mask uint8 [B,F], ident uint8 [B,F,F]; cls_att (optional) [(B*H), 1+F*n] = the cls query's probabilities.
  * out_planes (optional, mode 0 / 1): plane tensor of out [B*(1+F*n)][H*64] (mt_gemm_planes), written by the same kernels -- the
- * operand of the out-projection and of its weight gradient; out may then be NULL. */
+ * operand of the out-projection and of its weight gradient; out may then be NULL.
+ * n (patches per frame) = 1 .. 100: cls + n <= 64 keys run the 2 x 2-tile space kernels, 64 <= n <= 100 the query-walking ones;
+ * any other n returns MT_ERR_UNSUPPORTED before anything is launched (no output is written). */
 int mt_attn_fwd(const float* qkv, float* out, float* cls_att, const uint8_t* mask, const uint8_t* ident,
                 int B, int H, int F, int n, int mode, float scale, void* out_planes, void* stream);
 
@@ -377,7 +379,10 @@ int mt_embed_bwd(const float* dx, float* dcls, float* dpos_emb, float* dsize_emb
  * mode 2 reads row 0 of dout only and writes dk / dv of every row and dq of row 0 of each clip; the dq section (columns [0, H*64)) of
  * the patch rows is NOT written and keeps what it held -- a caller that reads it zero-fills it first.
  * dqkv_planes (optional, mode 0 / 1): the result as a plane tensor [B*N][3*H*64] (operand of the QKV layer's data and weight
- * gradients).  dqkv is then working memory: its patch rows are left holding the cls query's contribution only. */
+ * gradients).  dqkv is then working memory: its patch rows are left holding the cls query's contribution only.
+ * n = 1 .. 100 like mt_attn_fwd (any other n: MT_ERR_UNSUPPORTED, nothing written).  One wavefront owns a whole (b, head, frame) /
+ * (b, head, patch) group at every n: patch rows have one writer, the cls key's row takes atomics or, in deterministic mode, a
+ * fixed-order reduction with one rank per group. */
 int mt_attn_bwd(const float* qkv, const float* dout, float* dqkv, const uint8_t* mask, const uint8_t* ident,
                 int B, int H, int F, int n, int mode, float scale, void* dqkv_planes, void* stream);
 

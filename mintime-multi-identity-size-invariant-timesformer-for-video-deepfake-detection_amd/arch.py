@@ -120,12 +120,13 @@ def effnet_b0_state_spec(include_top: bool = True, num_classes: int = 1000):
 # Size-Invariant TimeSformer
 # ---------------------------------------------------------------------------------------------
 
-def default_tsf_config(channels: int = 1280, num_frames: int = 8):
+def default_tsf_config(channels: int = 1280, num_frames: int = 8, num_patches: int = 49, image_size: int = 224):
     """The shipped config/size_invariant_timesformer.yaml:15-32 with the two overrides the
-    EfficientNet variant needs (channels 1280, num-frames 8)."""
+    EfficientNet variant needs (channels 1280, num-frames 8).  num_patches is the extractor's feature-map area at
+    image_size (EfficientNet-B0: (image_size / 32)^2 -- 49 at 224, 64 at 256; Xception at 299: 100); 1..100 are accepted."""
     return {
         "model": {
-            "image-size": 224, "patch-size": 1, "num-classes": 1, "num-patches": 49,
+            "image-size": image_size, "patch-size": 1, "num-classes": 1, "num-patches": num_patches,
             "num-frames": num_frames, "max-identities": 2, "dim": 512, "depth": 9,
             "dim-head": 64, "channels": channels, "heads": 8, "attn-dropout": 0.0,
             "ff-dropout": 0.0, "shift-tokens": False, "enable-size-emb": True,

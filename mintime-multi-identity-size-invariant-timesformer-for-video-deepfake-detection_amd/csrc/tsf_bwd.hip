@@ -1024,6 +1024,232 @@ __global__ __launch_bounds__(WPB * 64) void attn_space_bwd_mfma_kernel(const flo
   }
 }
 
+// Space attention backward for 64 <= n <= 100 patches: NK = 3 or 4 key tiles of 32 (cls + n keys <= 128), the queries walked in tiles
+// of 32 (attn_space_fwd_mfma_wide_kernel is the forward twin).  ONE wavefront still owns a whole (b, h, frame) group, so the
+// ownership of the results is that of the 2 x 2 kernel: dq stored, a patch key's dk / dv a plain read-modify-write by this wavefront,
+// the cls key's row by fp32 atomics or, in deterministic mode, through the log with one rank per group (rank = frame).
+//   phase A, per query tile, lane = query:  S^T, dP^T against all NK key tiles -> P^T, delta, dS^T in-lane -> dQ^T = K^T dS^T, key tile
+//            by key tile (K by columns, 16 steps each); the query's (row max, 1 / sum, delta) go to 1.5 KB of LDS per wavefront
+//   phase B, per key tile, lane = key:  for every query tile recompute S and dP (the same products in the same order as phase A:
+//            the same bits), P = exp(S - max) / sum and dS from the statistics, and accumulate dV^T += dO^T P, dK^T += (sQ)^T dS
+// A 128 x 128 P^T and dS^T do not fit 160 KB of LDS four wavefronts to a block, hence the recomputation (the non-XP form of the 2 x 2
+// kernel); 64 NK + 64 MFMAs per query tile in phase A and 128 per (key tile, query tile) in phase B.
+template <int WPB, int NK, bool FACT>
+__global__ __launch_bounds__(WPB * 64) void attn_space_bwd_mfma_wide_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
+                                                                           float* __restrict__ dqkv, int B, int H, int F, int n,
+                                                                           float scale, const PlaneRef dp, const DetLog det) {
+  __shared__ float2 stat_all[WPB][128];                     // (row max, 1 / sum) per query of the wavefront's group
+  __shared__ float delta_all[WPB][128];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = lane & 31, hf = lane >> 5;
+  float2* stat = stat_all[wave];
+  float* dlt = delta_all[wave];
+  const int N = 1 + F * n, inner = H * DH, ld = 3 * inner;
+  const int64_t wid = (int64_t)blockIdx.x * WPB + wave;
+  if (wid >= (int64_t)B * H * F) return;                    // wave-uniform (no block-level barrier below)
+  const int f = (int)(wid % F);
+  const int bh = (int)(wid / F);
+  const int h = bh % H, b = bh / H;
+  const float* base = qkv + (int64_t)b * N * ld + h * DH;
+  float* dbase = dqkv + (int64_t)b * N * ld + h * DH;
+  const float* dobase = dout + (int64_t)b * N * inner + h * DH;
+  const int t0 = 1 + f * n;
+  auto tok_k = [&](int key) { return key == 0 ? 0 : t0 + min(key, n) - 1; };
+  auto tok_q = [&](int q) { return t0 + min(q, n - 1); };
+  const int nq = (n + 31) >> 5;                             // query tiles (<= 4)
+
+  // ---------------------------------------------------------------- phase A: lane = query (32 j + c)
+#pragma unroll 1
+  for (int j = 0; j < nq; ++j) {
+    const int q = 32 * j + c;
+    // K and V do not depend on the query tile, and hoisted out of this loop their 96 NK registers per lane spill: the loads below go
+    // through an offset (zero) the compiler cannot see through, so each trip reads them again (from L2: 50 KB per group)
+    int again = 0;
+    asm volatile("" : "+s"(again));
+    const float* kvb = base + again;
+    float qb[32], dob[32];
+    load_row32(base + (int64_t)tok_q(q) * ld + hf * 32, qb, scale);
+    load_row32(dobase + (int64_t)tok_q(q) * inner + hf * 32, dob, 1.0f);
+    f32x16 st[NK], dpt[NK];
+#pragma unroll
+    for (int i = 0; i < NK; ++i) {
+      float ka[32], va[32];
+      load_row32(kvb + (int64_t)tok_k(32 * i + c) * ld + inner + hf * 32, ka, 1.0f);
+      load_row32(kvb + (int64_t)tok_k(32 * i + c) * ld + 2 * inner + hf * 32, va, 1.0f);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { st[i][r] = 0.f; dpt[i][r] = 0.f; }
+#pragma unroll
+      for (int ks = 0; ks < 32; ++ks) {
+        st[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[ks], qb[ks], st[i], 0, 0, 0);
+        dpt[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[ks], dob[ks], dpt[i], 0, 0, 0);
+      }
+    }
+    float mx = -FLT_MAX;
+#pragma unroll
+    for (int i = 0; i < NK; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (32 * i + mfma_slot_row(r, hf) <= n) mx = fmaxf(mx, st[i][r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < NK; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float e = (32 * i + mfma_slot_row(r, hf) <= n) ? __expf(st[i][r] - mx) : 0.f;
+        st[i][r] = e;
+        sum += e;
+      }
+    sum += __shfl_xor(sum, 32);
+    const float inv = 1.0f / sum;
+    float delta = 0.f;
+#pragma unroll
+    for (int i = 0; i < NK; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { st[i][r] *= inv; delta = fmaf(st[i][r], dpt[i][r], delta); }
+    delta += __shfl_xor(delta, 32);
+#pragma unroll
+    for (int i = 0; i < NK; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) st[i][r] *= dpt[i][r] - delta;          // dS^T (zero on padded keys: P^T is zero there)
+    if (hf == 0) { stat[q] = make_float2(mx, inv); dlt[q] = delta; }
+    f32x16 dq[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dq[i][r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < NK; ++i) {
+      float kc[2][16];                       // K by columns in the order this key tile's dS^T accumulator is consumed in
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) {
+        const float* kr = kvb + (int64_t)tok_k(32 * i + mfma_slot_row(ks, hf)) * ld + inner;
+        kc[0][ks] = kr[c];
+        kc[1][ks] = kr[32 + c];
+      }
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks)
+#pragma unroll
+        for (int d = 0; d < 2; ++d) dq[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(kc[d][ks], st[i][ks], dq[d], 0, 0, 0);
+    }
+    if (q < n) {
+      float* drow = dbase + (int64_t)(t0 + q) * ld;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float4 v = make_float4(scale * dq[i][4 * g], scale * dq[i][4 * g + 1], scale * dq[i][4 * g + 2], scale * dq[i][4 * g + 3]);
+          if (dp.p) planes_store4(dp, b * N + t0 + q, h * DH + 32 * i + 8 * g + 4 * hf, v.x, v.y, v.z, v.w);   // final: nothing else writes a patch row's dq
+          else *reinterpret_cast<float4*>(drow + 32 * i + 8 * g + 4 * hf) = v;
+        }
+    }
+  }
+  __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): the statistics are in LDS
+  __builtin_amdgcn_wave_barrier();
+
+  // ---------------------------------------------------------------- phase B: lane = key (32 j + c)
+#pragma unroll 1
+  for (int j = 0; j < NK; ++j) {
+    const int key = 32 * j + c;
+    float kb[32], vb[32];
+    load_row32(base + (int64_t)tok_k(key) * ld + inner + hf * 32, kb, 1.0f);
+    load_row32(base + (int64_t)tok_k(key) * ld + 2 * inner + hf * 32, vb, 1.0f);
+    f32x16 dv[2], dk[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { dv[i][r] = 0.f; dk[i][r] = 0.f; }
+#pragma unroll 1
+    for (int i = 0; i < nq; ++i) {
+      f32x16 pp, ds;                          // P and dS of query tile i
+      {
+        float qa[32], da[32];
+        load_row32(base + (int64_t)tok_q(32 * i + c) * ld + hf * 32, qa, scale);
+        load_row32(dobase + (int64_t)tok_q(32 * i + c) * inner + hf * 32, da, 1.0f);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { pp[r] = 0.f; ds[r] = 0.f; }
+#pragma unroll
+        for (int ks = 0; ks < 32; ++ks) {
+          pp = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[ks], kb[ks], pp, 0, 0, 0);
+          ds = __builtin_amdgcn_mfma_f32_32x32x2f32(da[ks], vb[ks], ds, 0, 0, 0);
+        }
+      }
+      // dO and scaled Q by columns, in the query order the P / dS accumulators are consumed in
+      float dc[2][16], qc[2][16];
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) {
+        const int tq = tok_q(32 * i + mfma_slot_row(ks, hf));
+        const float* dr = dobase + (int64_t)tq * inner;
+        const float* qr = base + (int64_t)tq * ld;
+        dc[0][ks] = dr[c]; dc[1][ks] = dr[32 + c];
+        qc[0][ks] = qr[c] * scale; qc[1][ks] = qr[32 + c] * scale;
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int q = 32 * i + mfma_slot_row(r, hf);
+        const float2 sd = stat[q];
+        const float p = (q < n && key <= n) ? __expf(pp[r] - sd.x) * sd.y : 0.f;   // (padded query slots hold copies of the last query)
+        ds[r] = p * (ds[r] - dlt[q]);
+        pp[r] = p;
+      }
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks)
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+          dv[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(dc[d][ks], pp[ks], dv[d], 0, 0, 0);
+          dk[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(qc[d][ks], ds[ks], dk[d], 0, 0, 0);
+        }
+    }
+    if (key <= n) {
+      float* krow = dbase + (int64_t)tok_k(key) * ld + inner;
+      float* vrow = dbase + (int64_t)tok_k(key) * ld + 2 * inner;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int d0 = 32 * i + 8 * g + 4 * hf;
+          if (key == 0) {                       // the cls key is shared by every frame of the clip
+            if (det.vals) {                     // deterministic mode: one log row per frame, summed in frame order (det.hpp)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) { det_put(det, 2 * bh, f, d0 + e, dk[i][4 * g + e]); det_put(det, 2 * bh + 1, f, d0 + e, dv[i][4 * g + e]); }
+              if (f == 0 && d0 == 0) {
+                det_base(det, 2 * bh, (int64_t)b * N * ld + h * DH + inner);
+                det_base(det, 2 * bh + 1, (int64_t)b * N * ld + h * DH + 2 * inner);
+              }
+            } else {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) { atomicAdd(krow + d0 + e, dk[i][4 * g + e]); atomicAdd(vrow + d0 + e, dv[i][4 * g + e]); }
+            }
+          } else {
+            float4 a, v;
+            if constexpr (FACT) {               // the cls query's rank-1 contribution from its two scalars (attn_cls_bwd_kernel, factored)
+              // (the same two roundings as the full rows the non-factored kernel stores: dS * (q * scale), p * dO; no contraction)
+              const float* dclip = dqkv + (int64_t)b * N * ld;
+              const float dsc = dclip[cls_fact_off(0, h, H, tok_k(key), N, inner, ld)];
+              const float pc = dclip[cls_fact_off(1, h, H, tok_k(key), N, inner, ld)];
+              const float4 qc = *reinterpret_cast<const float4*>(base + d0), dc = *reinterpret_cast<const float4*>(dobase + d0);
+              a = make_float4(mul_unfused(dsc, mul_unfused(qc.x, scale)), mul_unfused(dsc, mul_unfused(qc.y, scale)),
+                              mul_unfused(dsc, mul_unfused(qc.z, scale)), mul_unfused(dsc, mul_unfused(qc.w, scale)));
+              v = make_float4(mul_unfused(pc, dc.x), mul_unfused(pc, dc.y), mul_unfused(pc, dc.z), mul_unfused(pc, dc.w));
+            } else {
+              a = *reinterpret_cast<const float4*>(krow + d0); v = *reinterpret_cast<const float4*>(vrow + d0);
+            }
+            a.x += dk[i][4 * g]; a.y += dk[i][4 * g + 1]; a.z += dk[i][4 * g + 2]; a.w += dk[i][4 * g + 3];
+            v.x += dv[i][4 * g]; v.y += dv[i][4 * g + 1]; v.z += dv[i][4 * g + 2]; v.w += dv[i][4 * g + 3];
+            if (dp.p) {                           // the group owns its patch keys: these are the final dk / dv values
+              const int row = b * N + tok_k(key);
+              planes_store4(dp, row, inner + h * DH + d0, a.x, a.y, a.z, a.w);
+              planes_store4(dp, row, 2 * inner + h * DH + d0, v.x, v.y, v.z, v.w);
+            } else {
+              *reinterpret_cast<float4*>(krow + d0) = a;
+              *reinterpret_cast<float4*>(vrow + d0) = v;
+            }
+          }
+        }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------- attention backward: patch queries
 // Same decomposition as the forward kernel (one lane per query; MODE 0 time / 1 space).
 // pass 1 (lane = query i): s_ij, p_ij, dP_ij = dO_i.v_j, delta_i, dS_ij = p_ij(dP_ij - delta_i), dq_i = scale*sum_j dS_ij k_j
@@ -1675,7 +1901,7 @@ extern "C" int mt_attn_bwd(const float* qkv, const float* dout, float* dqkv, con
                            int B, int H, int F, int n, int mode, float scale, void* dqkv_planes, void* stream) {
   if (!qkv || !dout || !dqkv) return fail(MT_ERR_ARG, "mt_attn_bwd: null pointer");
   if (mode == 0 && (!mask || !ident)) return fail(MT_ERR_ARG, "mt_attn_bwd: time attention needs mask and identities_mask");
-  if (n != 49) return fail(MT_ERR_UNSUPPORTED, "mt_attn_bwd: num-patches %d unsupported (49)", n);
+  if (n < 1 || n > 100) return fail(MT_ERR_UNSUPPORTED, "mt_attn_bwd: num-patches %d unsupported (1..100)", n);
   if (dqkv_planes && (mode == 2 || ((uintptr_t)dqkv_planes & 15))) return fail(MT_ERR_ARG, "mt_attn_bwd: plane output needs mode 0 / 1 and 16-byte alignment");
   hipStream_t s = (hipStream_t)stream;
   const int N = 1 + F * n;
@@ -1683,10 +1909,14 @@ extern "C" int mt_attn_bwd(const float* qkv, const float* dout, float* dqkv, con
   const PlaneRef dp{reinterpret_cast<__bf16*>(dqkv_planes), (int64_t)rp * ld, ld / 16, rp};
   static const bool time_old = env_set("MT_ATTN_TIME_OLD");    // A/B aid: the 7-patches-per-wavefront kernel
   static const bool valu = env_set("MT_ATTN_VALU");            // A/B aid: the one-lane-per-query space kernel
+  if (mode == 1 && valu && n != 49) return fail(MT_ERR_UNSUPPORTED, "mt_attn_bwd: MT_ATTN_VALU holds num-patches 49 only (got %d)", n);
   static const bool fact_on = env_int("MT_ATTN_CLS_FACT", 1) != 0;
   // with plane output the fp32 dqkv is working memory: the cls query's contribution to the patch keys crosses to the patch kernel as two
   // scalars per key and head (kernels that understand it: the MFMA space kernel, the one-patch-per-wavefront time kernel)
-  const bool fact = fact_on && dqkv_planes && ((mode == 1 && !valu) || (mode == 0 && !time_old && (F == 8 || F == 16)));
+  // The scalars park in 2 H ceil(N / inner) of the clip's own N - 1 patch rows (cls_fact_off): a clip with fewer patch rows than that
+  // (few patches, many heads) takes the full-row form, or the scalars would land in the next clip and past the buffer.
+  const bool fact_fits = (int64_t)2 * H * ((N + H * DH - 1) / (H * DH)) <= N - 1;
+  const bool fact = fact_on && fact_fits && dqkv_planes && ((mode == 1 && !valu) || (mode == 0 && !time_old && (F == 8 || F == 16)));
   hipLaunchKernelGGL(attn_cls_bwd_kernel, dim3(B * H), dim3(CLS_W * 64), (2 * N + CLS_W + 4 + CLS_W * 64) * sizeof(float), s, qkv, dout, dqkv, mask, B, H, F, n, scale, fact ? 1 : 0);
   int rc = check_launch("mt_attn_bwd(cls)");
   if (rc || mode == 2) return rc;                 // mode 2: the cls query's adjoint only (dk / dv of every key, dq of the cls row)
@@ -1700,7 +1930,14 @@ extern "C" int mt_attn_bwd(const float* qkv, const float* dout, float* dqkv, con
       const int64_t waves = (int64_t)B * H * F;
       static const bool xp = env_int("MT_ATTN_SPACE_XP", 1) != 0;    // 0: phase B recomputes P / dS (round 5)
       const dim3 grid((unsigned)((waves + 3) / 4));
-      if (xp) {
+      // cls + n keys: up to 64 fit the 2 x 2 tiles; 65..96 take three key tiles, 97..101 four, with the queries walked in tiles
+      if (n + 1 > 96) {
+        if (fact) hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 4, true>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
+        else hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 4, false>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
+      } else if (n + 1 > 64) {
+        if (fact) hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 3, true>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
+        else hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 3, false>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
+      } else if (xp) {
         constexpr size_t lds = (size_t)4 * 2 * 64 * XP_LD * sizeof(float);
         auto k = fact ? attn_space_bwd_mfma_kernel<4, true, true> : attn_space_bwd_mfma_kernel<4, false, true>;
         if (ensure_dynamic_lds((const void*)k, lds) != hipSuccess) return fail(MT_ERR_LAUNCH, "mt_attn_bwd(space): %zu bytes of LDS refused", lds);

@@ -485,6 +485,112 @@ __global__ __launch_bounds__(WPB * 64) void attn_space_fwd_mfma_kernel(const flo
   }
 }
 
+// Space attention for 64 <= n <= 100 patches: the same transposed formulation with NK = 3 or 4 key tiles of 32 (cls + n keys <= 128)
+// and the queries WALKED in tiles of 32.  One wavefront still owns a whole (b, h, frame) group: K (by rows) and V (by columns, in the
+// order the accumulators are consumed in) are read once and stay in registers (2 x 32 NK floats per lane), and each trip of the query
+// loop loads 32 queries, forms their S^T against all NK key tiles (so the softmax of a query sees every key: its row max and sum run
+// over the NK x 16 accumulator slots of one lane + one xor-32 exchange), then O^T, and stores.  Padding keys (key > n) get probability
+// exactly 0; padding queries (q >= n, copies of the last query) are computed and never stored.  48 NK MFMAs per query tile.
+template <int WPB, int NK>
+__global__ __launch_bounds__(WPB * 64) void attn_space_fwd_mfma_wide_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                                           int B, int H, int F, int n, float scale, const PlaneRef op) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = lane & 31, hf = lane >> 5;
+  const int N = 1 + F * n, inner = H * DH, ld = 3 * inner;
+  const int64_t wid = (int64_t)blockIdx.x * WPB + wave;
+  if (wid >= (int64_t)B * H * F) return;                 // wave-uniform
+  const int f = (int)(wid % F);
+  const int bh = (int)(wid / F);
+  const int h = bh % H, b = bh / H;
+  const float* base = qkv + (int64_t)b * N * ld + h * DH;
+  const int t0 = 1 + f * n;
+  auto tok_k = [&](int key) { return key == 0 ? 0 : t0 + min(key, n) - 1; };   // keys >= n+1 are padding (masked below)
+  auto tok_q = [&](int q) { return t0 + min(q, n - 1); };
+
+  float ka[NK][32], va[2][16 * NK];
+#pragma unroll
+  for (int i = 0; i < NK; ++i) {
+    const float* kr = base + (int64_t)tok_k(32 * i + c) * ld + inner + hf * 32;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const float4 kk = *reinterpret_cast<const float4*>(kr + 4 * t);
+      ka[i][4 * t] = kk.x; ka[i][4 * t + 1] = kk.y; ka[i][4 * t + 2] = kk.z; ka[i][4 * t + 3] = kk.w;
+    }
+  }
+#pragma unroll
+  for (int ks = 0; ks < 16 * NK; ++ks) {
+    const int key = 32 * (ks >> 4) + mfma_slot_row(ks & 15, hf);
+    const float* vr = base + (int64_t)tok_k(key) * ld + 2 * inner;
+    va[0][ks] = vr[c];
+    va[1][ks] = vr[32 + c];
+  }
+
+  const int nq = (n + 31) >> 5;                           // query tiles
+#pragma unroll 1
+  for (int j = 0; j < nq; ++j) {
+    const int q = 32 * j + c;
+    float qb[32];
+    {
+      const float* qr = base + (int64_t)tok_q(q) * ld + hf * 32;
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        const float4 qq = *reinterpret_cast<const float4*>(qr + 4 * t);
+        qb[4 * t] = qq.x * scale; qb[4 * t + 1] = qq.y * scale; qb[4 * t + 2] = qq.z * scale; qb[4 * t + 3] = qq.w * scale;
+      }
+    }
+    f32x16 st[NK];                                        // S^T tiles [key tile] of this query tile
+#pragma unroll
+    for (int i = 0; i < NK; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) st[i][r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 32; ++ks)
+#pragma unroll
+      for (int i = 0; i < NK; ++i) st[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[i][ks], qb[ks], st[i], 0, 0, 0);
+
+    float mx = -FLT_MAX;
+#pragma unroll
+    for (int i = 0; i < NK; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (32 * i + mfma_slot_row(r, hf) <= n) mx = fmaxf(mx, st[i][r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < NK; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p = (32 * i + mfma_slot_row(r, hf) <= n) ? __expf(st[i][r] - mx) : 0.f;
+        st[i][r] = p;
+        sum += p;
+      }
+    sum += __shfl_xor(sum, 32);
+    const float inv = 1.0f / sum;
+
+    f32x16 ot[2];                                         // O^T tiles [d tile]
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ot[i][r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 16 * NK; ++ks)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) ot[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[i][ks], st[ks >> 4][ks & 15], ot[i], 0, 0, 0);
+
+    if (q < n) {
+      float* orow = out ? out + ((int64_t)b * N + t0 + q) * inner + h * DH : nullptr;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {        // slots 4g..4g+3 are d = 32 i + 8 g + 4 half + (0..3)
+          const float o0 = ot[i][4 * g] * inv, o1 = ot[i][4 * g + 1] * inv, o2 = ot[i][4 * g + 2] * inv, o3 = ot[i][4 * g + 3] * inv;
+          if (orow) *reinterpret_cast<float4*>(orow + 32 * i + 8 * g + 4 * hf) = make_float4(o0, o1, o2, o3);
+          if (op.p) planes_store4(op, b * N + t0 + q, h * DH + 32 * i + 8 * g + 4 * hf, o0, o1, o2, o3);
+        }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------- attention: cls query
 // one block of CLS_W wavefronts per (b,h): the (scaled) cls query attends to all N keys, padded frames masked (:120, :259-260).
 // Keys are spread over all the block's lanes for the scores (one 256-byte K row per lane) and over its wavefronts for the
@@ -666,7 +772,9 @@ extern "C" int mt_attn_fwd(const float* qkv, float* out, float* cls_att, const u
   if (!qkv || (!out && !out_planes)) return fail(MT_ERR_ARG, "mt_attn_fwd: null pointer");
   if (out_planes && (mode == 2 || ((uintptr_t)out_planes & 15))) return fail(MT_ERR_ARG, "mt_attn_fwd: plane output needs mode 0 / 1 and 16-byte alignment");
   if (mode == 0 && (!mask || !ident)) return fail(MT_ERR_ARG, "mt_attn_fwd: time attention needs mask and identities_mask");
-  if (n != 49) return fail(MT_ERR_UNSUPPORTED, "mt_attn_fwd: num-patches %d unsupported (49)", n);
+  if (n < 1 || n > 100) return fail(MT_ERR_UNSUPPORTED, "mt_attn_fwd: num-patches %d unsupported (1..100)", n);
+  static const bool valu = env_set("MT_ATTN_VALU");       // A/B aid: the one-lane-per-query space kernel (built for 50 keys)
+  if (mode == 1 && valu && n != 49) return fail(MT_ERR_UNSUPPORTED, "mt_attn_fwd: MT_ATTN_VALU holds num-patches 49 only (got %d)", n);
   hipStream_t s = (hipStream_t)stream;
   const int N = 1 + F * n;
   const int rp = (B * N + 31) & ~31;
@@ -675,10 +783,12 @@ extern "C" int mt_attn_fwd(const float* qkv, float* out, float* cls_att, const u
   int rc = check_launch("mt_attn_fwd(cls)");
   if (rc || mode == 2) return rc;                 // mode 2: the cls query only (out row 0 of every clip; the patch rows are not written)
   if (mode == 1) {
-    static const bool valu = env_set("MT_ATTN_VALU");     // A/B aid: the one-lane-per-query kernel
     if (valu) return launch_patch<1, 50, 1, 64, 2>(qkv, out, mask, ident, B, H, F, n, scale, op, s);
     const int64_t waves = (int64_t)B * H * F;
-    hipLaunchKernelGGL(attn_space_fwd_mfma_kernel<4>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, qkv, out, B, H, F, n, scale, op);
+    // cls + n keys: up to 64 fit the 2 x 2 tiles; 65..96 take three key tiles, 97..101 four, with the queries walked in tiles
+    if (n + 1 > 96) hipLaunchKernelGGL((attn_space_fwd_mfma_wide_kernel<4, 4>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, qkv, out, B, H, F, n, scale, op);
+    else if (n + 1 > 64) hipLaunchKernelGGL((attn_space_fwd_mfma_wide_kernel<4, 3>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, qkv, out, B, H, F, n, scale, op);
+    else hipLaunchKernelGGL(attn_space_fwd_mfma_kernel<4>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, qkv, out, B, H, F, n, scale, op);
     return check_launch("mt_attn_fwd(space, mfma)");
   }
   static const bool time_old = env_set("MT_ATTN_TIME_OLD");    // A/B aid: the 7-patches-per-wavefront kernel

@@ -96,7 +96,7 @@ class OverlappedGradReducer:
         """live_rows: {parameter: n} -- only the first n rows of that (embedding-table) parameter ever receive gradient: the rest
         of its gradient is exactly zero on every rank and is left out of the collective.  The TimeSformer's two tables are
         [num_frames * channels + 1, dim] = 21 MB each (the reference's (sic) sizing, size_invariant_timesformer.py:172-180) while
-        positions only reach F * 49 and size buckets 20 (deepfakes_dataset.py:259-263,324-329): 42 of the bucket's 234 MB.  The
+        positions only reach F * num-patches (F * 49 at 224 x 224 crops) and size buckets 20 (deepfakes_dataset.py:259-263,324-329): 42 of the bucket's 234 MB.  The
         bound is the caller's data contract; the first `LIVE_ROW_CHECKS` engine launches verify that the skipped rows are zero."""
         self.group = group
         self.sync = True

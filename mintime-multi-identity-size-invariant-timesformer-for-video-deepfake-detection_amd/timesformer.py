@@ -114,8 +114,15 @@ class SizeInvariantTimeSformer(nn.Module):
         self.dropout_uniform = None
         if self.dim_head != 64:
             raise NotImplementedError("dim-head must be 64 (the attention kernels are specialised for it)")
+        if not 1 <= int(self.num_patches) <= 100:
+            raise NotImplementedError(f"num-patches must be in 1..100 (the space-attention kernels hold cls + 100 keys), got {self.num_patches}")
 
         num_positions = self.num_frames * self.channels          # (sic) reference :172 -- keeps state-dict shapes
+        if self.num_frames * self.num_patches + 1 > num_positions + 1:
+            # positions run up to num-frames * num-patches (deepfakes_dataset.py:259-263); the reference's nn.Embedding would raise an
+            # index error at the first forward
+            raise ValueError(f"num-frames * num-patches + 1 = {self.num_frames * self.num_patches + 1} positions do not fit pos_emb's "
+                             f"{num_positions + 1} rows (num-frames * channels + 1)")
         self.to_patch_embedding = _Linear(self.channels, self.dim)
         self.cls_token = nn.Parameter(torch.empty(1, self.dim))
         self.pos_emb = _Embedding(num_positions + 1, self.dim)

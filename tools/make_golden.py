@@ -7,6 +7,7 @@ reference's source enters the repo: the fixtures are inputs' checksums and outpu
 
     python tools/make_golden.py            # writes every fixture
     GOLDEN_ONLY=baseline python tools/make_golden.py   # only baseline_head.npz and baseline_e2e_train.npz (`--model 0`)
+    GOLDEN_ONLY=patches python tools/make_golden.py    # only tsf_p16.npz and tsf_p64.npz (num-patches 16 and 64)
 """
 import json
 import os
@@ -104,12 +105,13 @@ def build_tsf(TSF, cfg, seed, require_attention, dtype=torch.float32):
     return model.to(dtype), sd
 
 
-def tsf_case(TSF, name, batch, frames, channels, identities, ragged, seed, pos_emb=True, size_emb=True):
-    cfg = arch.default_tsf_config(channels=channels, num_frames=frames)
+def tsf_case(TSF, name, batch, frames, channels, identities, ragged, seed, pos_emb=True, size_emb=True, hw=7):
+    """hw: side of the extractor's feature map; num-patches = hw * hw (7 -> the shipped 49)."""
+    cfg = arch.default_tsf_config(channels=channels, num_frames=frames, num_patches=hw * hw, image_size=32 * hw)
     cfg["model"]["enable-pos-emb"], cfg["model"]["enable-size-emb"] = pos_emb, size_emb   # size_invariant_timesformer.py:235-248
     model, sd = build_tsf(TSF, cfg, seed, True)
-    feats = synth.features(batch, frames, channels, seed)
-    aux = synth.clip_inputs(batch, frames, identities, seed, ragged=ragged, with_video=False)
+    feats = synth.features(batch, frames, channels, seed, hw=hw)
+    aux = synth.clip_inputs(batch, frames, identities, seed, ragged=ragged, with_video=False, num_patches=hw * hw)
     rows = []
     hooks = []
     for i in range(1, cfg["model"]["depth"]):
@@ -149,7 +151,7 @@ def tsf_case(TSF, name, batch, frames, channels, identities, ragged, seed, pos_e
          feats_sum=checksum(feats), loss=loss.detach(), dfeats_norm=feats_g.grad.norm(),
          dfeats_slice=feats_g.grad.permute(0, 1, 3, 4, 2).reshape(-1)[:512].clone(),
          batch=batch, frames=frames, channels=channels, identities=identities, ragged=int(ragged), seed=seed,
-         pos_emb=int(pos_emb), size_emb=int(size_emb), **grads)
+         pos_emb=int(pos_emb), size_emb=int(size_emb), hw=hw, **grads)
 
 
 def tsf_dropout_case(TSF, name, batch, frames, channels, identities, seed, depth=3, attn_p=0.1, ff_p=0.2):
@@ -631,7 +633,10 @@ def main():
         tsf_case(TSF, "tsf_cfg1", batch=2, frames=8, channels=1280, identities=1, ragged=False, seed=0)
         tsf_case(TSF, "tsf_2id_ragged", batch=2, frames=8, channels=1280, identities=2, ragged=True, seed=1)
         tsf_case(TSF, "tsf_xs_3id", batch=1, frames=16, channels=2048, identities=3, ragged=True, seed=2)
-    if only in ("dc", "agg", "slots", "switch", "tsf", "dropout"):
+    if only in ("", "patches"):  # num-patches other than 49: 4 x 4 and 8 x 8 feature maps (EfficientNet-B0 at 128 and 256)
+        tsf_case(TSF, "tsf_p16", batch=2, frames=8, channels=1280, identities=2, ragged=True, seed=5, hw=4)
+        tsf_case(TSF, "tsf_p64", batch=2, frames=8, channels=1280, identities=2, ragged=True, seed=6, hw=8)
+    if only in ("dc", "agg", "slots", "switch", "tsf", "dropout", "patches"):
         return
     from models.xception import xception as _xc
     man["xception"] = [[k, list(v.shape), str(v.dtype)] for k, v in _xc(num_classes=1).state_dict().items()]
