@@ -297,7 +297,8 @@ int mt_se_pool_fwd(const float* z, const float* scale, const float* shift, float
 
 /* excite: pooled = sum of the slices (written to `pooled` [N,C] when not NULL: kept for backward);
  * gate = sigmoid(_se_expand(swish(_se_reduce(pooled)))) (model.py:109-112). w1 [CS,C], w2 [C,CS];
- * hidden [N,CS] (required: the hand-over between the kernel pair) receives the pre-activation of the squeeze layer, which backward keeps. */
+ * hidden [N,CS] (required: the hand-over between the kernel pair) receives the pre-activation of the squeeze layer, which backward keeps.
+ * CS = 1 .. 48 like mt_se_bwd (any other width: MT_ERR_UNSUPPORTED before anything is launched). */
 int mt_se_gate_fwd(const float* partial, int parts, const float* w1, const float* b1, const float* w2, const float* b2,
                    float* pooled, float* gate, float* hidden, int N, int C, int CS, void* stream);
 
@@ -436,7 +437,8 @@ int mt_dwconv_bwd_res2(const float* du, const float* z, const float* kabc, const
                        double* stats_in, int slots, float* dw, int N, int H, int W, int C, int k, int stride,
                        int parts, int act, const float* res_pre, const float* res_post, void* stream);
 
-/* _conv_stem weight gradient (accumulated, torch layout [32,3,3,3]); x [N,H,W,3]. */
+/* _conv_stem weight gradient (accumulated, torch layout [32,3,3,3]); x [N,H,W,3].  H and W of different parity (TF-SAME would pad
+ * the two axes differently in front) are MT_ERR_UNSUPPORTED, as in mt_stem_conv_fwd. */
 int mt_stem_conv_wgrad(const float* du, const float* z, const float* kabc, const void* x, int x_is_u8, float* dw, int N,
                        int H, int W, void* stream);   /* x fp32 or (x_is_u8) uint8 */
 /* ... of the unpadded stride-2 3x3 convolution (Xception's conv1); du, z [N,(H-3)/2+1,(W-3)/2+1,32]. */

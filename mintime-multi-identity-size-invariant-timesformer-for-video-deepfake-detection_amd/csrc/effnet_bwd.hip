@@ -1038,7 +1038,9 @@ static int stem_conv_wgrad(const float* du, const float* z, const float* kabc, c
   if (!du || !z || !kabc || !x || !dw) return fail(MT_ERR_ARG, "mt_stem_conv_wgrad: null pointer");
   if (valid && (H < 3 || W < 3)) return fail(MT_ERR_ARG, "mt_stem_conv_wgrad_valid: crops of at least 3 x 3");
   const int Ho = valid ? (H - 3) / 2 + 1 : (H + 1) / 2, Wo = valid ? (W - 3) / 2 + 1 : (W + 1) / 2;
-  const int padt = valid ? 0 : max((Ho - 1) * 2 + 3 - H, 0);
+  const int padt = valid ? 0 : max((Ho - 1) * 2 + 3 - H, 0), padt_w = valid ? 0 : max((Wo - 1) * 2 + 3 - W, 0);
+  // one leading pad serves both axes, as in mt_stem_conv_fwd, which refuses the same shapes (H and W of different parity)
+  if (padt / 2 != padt_w / 2) return fail(MT_ERR_UNSUPPORTED, "mt_stem_conv_wgrad: H and W must need the same leading padding");
   // (deterministic mode takes the outer-product kernel: the MFMA form meets its row groups with LDS atomics)
   if (Wo <= 128 && !det_enabled()) return stem_wgrad_mfma(du, z, kabc, x, x_is_u8, dw, N, H, W, Ho, Wo, padt / 2, (hipStream_t)stream);
   DetScope det((hipStream_t)stream, 1, 1024, 32 * 27, true, true);

@@ -47,7 +47,7 @@ template <int K, int S, int T, int ACT, int CC, int RC = 0>
 __global__ __launch_bounds__(256) void dwconv_tiled_kernel(const float* __restrict__ zin, const float* __restrict__ scale,
                                                            const float* __restrict__ shift, const float* __restrict__ w,
                                                            float* __restrict__ zout, double* __restrict__ stats, int slots,
-                                                           int N, int H, int W, int C, int Ho, int Wo, int pad0, PlaneRef po,
+                                                           int N, int H, int W, int C, int Ho, int Wo, int pad0, int pad1, PlaneRef po,
                                                            const float* __restrict__ we) {
   static_assert(RC == 0 || CC == 16, "the recompute yields 16-channel chunks");
   constexpr int CQN = CC / 4, NSLOT = 256 / CQN;
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void dwconv_tiled_kernel(const float* __restri
   auto fetch = [&](int64_t tile) {
     int n, ty, tx;
     tile_nyx(tile, ty_n, tx_n, n, ty, tx);
-    const int ih0 = ty * T * S - pad0, iw0 = tx * T * S - pad0;
+    const int ih0 = ty * T * S - pad0, iw0 = tx * T * S - pad1;      // TF-SAME pads each axis by its own size
     const float* img = RC ? zin + (int64_t)n * H * W * RC : zin + (int64_t)n * H * W * C + c0 + cq * 4;
     pre_ok = 0;
 #pragma unroll
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void dwconv_tiled_kernel(const float* __restri
 
 template <int K, int S, int T, int ACT, int CC, int RC = 0>
 int launch_dw_tiled(const float* zin, const float* scale, const float* shift, const float* w, float* zout, double* stats, int slots,
-                    int N, int H, int W, int C, int Ho, int Wo, int pad0, hipStream_t s, const PlaneRef& po,
+                    int N, int H, int W, int C, int Ho, int Wo, int pad0, int pad1, hipStream_t s, const PlaneRef& po,
                     const float* we = nullptr) {
   constexpr int IH = (T - 1) * S + K;
   constexpr int IWP = IH | 1;
@@ -209,21 +209,21 @@ int launch_dw_tiled(const float* zin, const float* scale, const float* shift, co
     if (e != hipSuccess) return fail(MT_ERR_LAUNCH, "mt_dwconv_fwd: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
   }
   hipLaunchKernelGGL(k, dim3(bx), dim3(256), lds, s, zin, scale, shift, w, zout, stats, slots != 0 ? slots : 1, N, H,
-                     W, C, Ho, Wo, pad0, po, we);
+                     W, C, Ho, Wo, pad0, pad1, po, we);
   return check_launch("mt_dwconv_fwd(tiled)");
 }
 
 template <int K, int S, int ACT>
 int launch_dw_tiled_any(const float* zin, const float* scale, const float* shift, const float* w, float* zout, double* stats,
-                        int slots, int N, int H, int W, int C, int Ho, int Wo, int pad0, hipStream_t s, const PlaneRef& po) {
+                        int slots, int N, int H, int W, int C, int Ho, int Wo, int pad0, int pad1, hipStream_t s, const PlaneRef& po) {
   static const int t7_mask = env_int("MT_DW_T7", 0);       // lab: bit 0 = 7 x 7 tiles in the forward kernel
   const bool t14 = Ho >= 14 && !(t7_mask & 1);
   if (C % 16 == 0) {
-    if (t14) return launch_dw_tiled<K, S, 14, ACT, 16>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad0, s, po);
-    return launch_dw_tiled<K, S, 7, ACT, 16>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad0, s, po);
+    if (t14) return launch_dw_tiled<K, S, 14, ACT, 16>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad0, pad1, s, po);
+    return launch_dw_tiled<K, S, 7, ACT, 16>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad0, pad1, s, po);
   }
-  if (t14) return launch_dw_tiled<K, S, 14, ACT, 8>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad0, s, po);
-  return launch_dw_tiled<K, S, 7, ACT, 8>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad0, s, po);
+  if (t14) return launch_dw_tiled<K, S, 14, ACT, 8>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad0, pad1, s, po);
+  return launch_dw_tiled<K, S, 7, ACT, 8>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad0, pad1, s, po);
 }
 
 // ------------------------------------------------------------------------------------------------ BatchNorm finalize
@@ -332,6 +332,8 @@ __global__ __launch_bounds__(256) void se_pool_kernel(const float* __restrict__ 
 // rows walked together (independent loads in flight), ceil(CS/16) blocks per image; (B) the gate, one block per (image, 128-channel
 // slab): the slab's W2 rows are copied coalesced into LDS ([128][CS+1], odd pitch) and multiplied from there.
 constexpr int SE_SLAB = 128;
+constexpr int SE_CS_MAX = 48;        // widest squeeze layer admitted (mt_se_bwd: CS_MAX)
+static_assert((SE_CS_MAX + SE_SLAB * (SE_CS_MAX + 1)) * sizeof(float) <= 48 * 1024, "se_gate_kernel's LDS must fit an unreserved launch");
 __global__ __launch_bounds__(256) void se_hidden_kernel(const float* __restrict__ partial, int parts, const float* __restrict__ w1,
                                                         const float* __restrict__ b1, float* __restrict__ pooled,
                                                         float* __restrict__ hidden, int C, int CS) {
@@ -424,10 +426,12 @@ template <int K, int S>
 int launch_dw(const float* zin, const float* scale, const float* shift, const float* w, float* zout, double* stats, int slots,
               int N, int H, int W, int C, int act, hipStream_t s, const PlaneRef& po) {
   const int Ho = (H + S - 1) / S, Wo = (W + S - 1) / S;
-  const int pad = max((Ho - 1) * S + K - H, 0) / 2;              // TF-SAME pad-before
-  if (act == 1) return launch_dw_tiled_any<K, S, 1>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad, s, po);
-  if (act == 2) return launch_dw_tiled_any<K, S, 2>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad, s, po);
-  return launch_dw_tiled_any<K, S, 0>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad, s, po);
+  // TF-SAME pad-before, per axis: at stride 2 an odd size pads (K - 1) / 2 in front and an even one (K - 2) / 2, so H and W of
+  // different parity (9 x 20) differ
+  const int pad = max((Ho - 1) * S + K - H, 0) / 2, padw = max((Wo - 1) * S + K - W, 0) / 2;
+  if (act == 1) return launch_dw_tiled_any<K, S, 1>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad, padw, s, po);
+  if (act == 2) return launch_dw_tiled_any<K, S, 2>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad, padw, s, po);
+  return launch_dw_tiled_any<K, S, 0>(zin, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad, padw, s, po);
 }
 
 int dwconv_fwd(const float* zin, const float* scale, const float* shift, const float* w, float* zout, double* stats, int slots, int N,
@@ -468,11 +472,11 @@ extern "C" int mt_dwconv_fwd_rc(const float* y, const float* we, int cin, const 
   if (!mt_dwconv_rc_supported(cin, C, k, stride, H))
     return fail(MT_ERR_UNSUPPORTED, "mt_dwconv_fwd_rc: no instance for k=%d stride=%d Cin=%d C=%d H=%d", k, stride, cin, C, H);
   const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
-  const int pad = max((Ho - 1) * stride + k - H, 0) / 2;
+  const int pad = max((Ho - 1) * stride + k - H, 0) / 2, padw = max((Wo - 1) * stride + k - W, 0) / 2;
   const PlaneRef po{nullptr, 0, 0, 0};
 #define MT_CASE(K_, S_, CIN_, T_)                                                                                              \
   if (k == K_ && stride == S_ && cin == CIN_)                                                                                  \
-    return launch_dw_tiled<K_, S_, T_, 1, 16, CIN_>(y, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad, (hipStream_t)stream, po, we);
+    return launch_dw_tiled<K_, S_, T_, 1, 16, CIN_>(y, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad, padw, (hipStream_t)stream, po, we);
   MT_DW_RC_INSTANCES(MT_CASE)
 #undef MT_CASE
   return fail(MT_ERR_UNSUPPORTED, "mt_dwconv_fwd_rc: no instance");
@@ -530,7 +534,9 @@ extern "C" int mt_se_pool_fwd(const float* z, const float* scale, const float* s
 extern "C" int mt_se_gate_fwd(const float* partial, int parts, const float* w1, const float* b1, const float* w2, const float* b2,
                               float* pooled, float* gate, float* hidden, int N, int C, int CS, void* stream) {
   if (!partial || !w1 || !b1 || !w2 || !b2 || !gate || !hidden || parts < 1) return fail(MT_ERR_ARG, "mt_se_gate_fwd: null pointer");
-  if (CS < 1 || CS > 256) return fail(MT_ERR_UNSUPPORTED, "mt_se_gate_fwd: squeeze width %d", CS);
+  // the gate kernel holds hid[CS] + a [128][CS+1] slab in dynamic LDS and no larger size is reserved for it: 48 (EfficientNet-B0's
+  // widest squeeze, mt_se_bwd's own limit) is 25 KB; a width past 94 would ask for more than the 48 KB a launch may take unreserved
+  if (CS < 1 || CS > SE_CS_MAX) return fail(MT_ERR_UNSUPPORTED, "mt_se_gate_fwd: squeeze width %d outside 1 .. %d", CS, SE_CS_MAX);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(se_hidden_kernel, dim3(N, (CS + 15) / 16), dim3(256), (size_t)C * sizeof(float), s, partial, parts, w1, b1, pooled,
                      hidden, C, CS);
