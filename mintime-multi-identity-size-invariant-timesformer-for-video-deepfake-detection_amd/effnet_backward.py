@@ -17,7 +17,9 @@ FUSED_DW = __import__("os").environ.get("MT_DW_FUSED", "3")
 # 3 passes over a block's expanded tensor (read z_d, read z_d, write du_d) instead of 6 (write da | read da, z_d | read da, z_d,
 # write du_d), two launches fewer -- and SLOWER on every block (profiles/r03_se_fused_epilogue_vs_streaming.txt: block 1
 # 406 -> 744 us, the 7x7 blocks 126 -> 193 us, step +1.3 ms): a one-tile-per-block GEMM with a load-z / swish / store epilogue
-# per lane-column runs at 1.3-3.2 TB/s where the float4 streaming kernels it replaces run at 4.5-5.5.  Parity-tested, opt-in.
+# per lane-column runs at 1.3-3.2 TB/s where the float4 streaming kernels it replaces run at 4.5-5.5.  Opt-in (MT_SE_FUSED=1; no test
+# runs the engine with it); the two epilogues themselves are parity-tested per kernel against fp64 on the register-staged and the
+# LDS-DMA kernels (tests/test_gpu_gemm_ops.py).
 SE_FUSED = __import__("os").environ.get("MT_SE_FUSED", "0") != "0"
 EXPAND_FUSED = __import__("os").environ.get("MT_EXPAND_FUSED", "1") != "0"
 WIDE_WGRAD = __import__("os").environ.get("MT_WIDE_WGRAD", "1") != "0"      # late-stage project-conv weight gradients: wide_wgrad.hip
