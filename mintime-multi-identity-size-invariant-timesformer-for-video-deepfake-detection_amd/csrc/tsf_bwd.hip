@@ -214,12 +214,7 @@ __device__ __forceinline__ void layernorm_bwd_rows_body(const float* __restrict_
   }
 }
 
-// D <= 512: capped at the 56 VGPRs that are free next to three weight-gradient waves (the allocator rounds their 146 up to 152)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56))) void layernorm_bwd_rows_kernel2(
-    const float* dy, const float* x, const float* stats, const float* gamma, float* dx, const float* dx_in, int rows, int D, PlaneRef dxp) {
-  layernorm_bwd_rows_body<2>(dy, x, stats, gamma, dx, dx_in, rows, D, dxp);
-}
-// D <= 512, operands kept in registers (the default next to the plane-operand weight gradients; MT_LN_ROWS_KEEP=0: the 56-VGPR form)
+// D <= 512: operands kept in registers
 __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel2k(
     const float* dy, const float* x, const float* stats, const float* gamma, float* dx, const float* dx_in, int rows, int D, PlaneRef dxp) {
   layernorm_bwd_rows_body<2, true>(dy, x, stats, gamma, dx, dx_in, rows, D, dxp);
@@ -513,30 +508,8 @@ __global__ void head_bwd_clips_kernel(const float* __restrict__ dlogits, const f
 
 // ---------------------------------------------------------------------------------------- embeddings backward
 // dcls += sum_b dx[b,0]; dpos[positions[b,t]] += dx[b,t]; dsize[size idx] += dx[b,t]   (atomics; tables pre-zeroed)
-__global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict__ dx, float* __restrict__ dcls,
-                                                        float* __restrict__ dpos, float* __restrict__ dsize,
-                                                        const int64_t* __restrict__ positions, const int* __restrict__ sizes,
-                                                        int B, int N, int n, int F, int D, int pos_rows, int size_rows) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= B * N) return;
-  const int b = row / N, t = row - b * N;
-  int64_t pi = positions ? positions[row] : (int64_t)t;
-  int si = 0;
-  if (t > 0 && sizes) si = sizes[b * F + (t - 1) / n];
-  pi = pi < 0 ? 0 : (pi >= pos_rows ? pos_rows - 1 : pi);          // same clamp as the forward (which raised the flag)
-  si = si < 0 ? 0 : (si >= size_rows ? size_rows - 1 : si);
-  const float* dr = dx + (int64_t)row * D;
-  for (int i = lane; i < D; i += 64) {
-    const float v = dr[i];
-    if (t == 0 && dcls) atomicAdd(dcls + i, v);
-    if (dpos) atomicAdd(dpos + pi * D + i, v);
-    if (dsize) atomicAdd(dsize + (int64_t)si * D + i, v);
-  }
-}
-
 // One block per (clip, frame slot): the n tokens of a slot share their size row, so the block sums them in registers and issues ONE
-// atomic per column for it (the row-per-wavefront kernel above sends B N D atomics at ~21 live rows: 600 adds per address); position
+// atomic per column for it (one atomic per token and column would send B N D of them at ~21 live rows: 600 adds per address); position
 // rows differ per token and keep one atomic each.  Block (b, 0) also carries the cls row.
 __global__ __launch_bounds__(256) void embed_bwd_slots_kernel(const float* __restrict__ dx, float* __restrict__ dcls,
                                                               float* __restrict__ dpos, float* __restrict__ dsize,
@@ -574,55 +547,20 @@ __global__ __launch_bounds__(256) void embed_bwd_slots_kernel(const float* __res
   }
 }
 
-// Deterministic mode: one wavefront per (table, 64 columns), one lane per column, walks the token rows in order and adds each RUN of
-// rows that share a table row to it (tokens of one frame share their position / size row, so runs are long): every element of the
-// tables has one writer and a fixed summation order.  ~B N sequential, pipelined 4-byte loads per lane.
-__global__ __launch_bounds__(64) void embed_bwd_det_kernel(const float* __restrict__ dx, float* __restrict__ dcls,
-                                                           float* __restrict__ dpos, float* __restrict__ dsize,
-                                                           const int64_t* __restrict__ positions, const int* __restrict__ sizes,
-                                                           int B, int N, int n, int F, int D, int pos_rows, int size_rows) {
+// Deterministic mode, cls token: one lane per column adds the B cls rows in clip order (one writer, a fixed summation order).
+__global__ __launch_bounds__(64) void embed_bwd_det_kernel(const float* __restrict__ dx, float* __restrict__ dcls, int B, int N, int D) {
   const int col = blockIdx.x * 64 + threadIdx.x;
-  const int kind = blockIdx.y;                           // 0: cls, 1: positions, 2: sizes
-  if (col >= D) return;
-  if (kind == 0) {
-    if (!dcls) return;
-    float acc = 0.f;
-    for (int b = 0; b < B; ++b) acc += dx[(int64_t)b * N * D + col];
-    dcls[col] += acc;
-    return;
-  }
-  float* dst = kind == 1 ? dpos : dsize;
-  if (!dst) return;
-  int cur = -1;
-  float run = 0.f;
-  int b = 0, t = 0;
-  for (int row = 0; row < B * N; ++row) {
-    int idx;
-    if (kind == 1) {
-      int64_t pi = positions ? positions[row] : (int64_t)t;
-      idx = (int)(pi < 0 ? 0 : (pi >= pos_rows ? pos_rows - 1 : pi));
-    } else {
-      int si = 0;
-      if (t > 0 && sizes) si = sizes[b * F + (t - 1) / n];
-      idx = si < 0 ? 0 : (si >= size_rows ? size_rows - 1 : si);
-    }
-    const float v = dx[(int64_t)row * D + col];
-    if (idx != cur) {
-      if (cur >= 0) dst[(int64_t)cur * D + col] += run;
-      cur = idx;
-      run = 0.f;
-    }
-    run += v;
-    if (++t == N) { t = 0; ++b; }
-  }
-  if (cur >= 0) dst[(int64_t)cur * D + col] += run;
+  if (col >= D || !dcls) return;
+  float acc = 0.f;
+  for (int b = 0; b < B; ++b) acc += dx[(int64_t)b * N * D + col];
+  dcls[col] += acc;
 }
 
-// Deterministic mode since round 5: the run walk above is one wavefront per 64 columns over all B N token rows -- 5.9 ms per step at
+// Deterministic mode, the two tables: an ordered walk over all B N token rows (one wavefront per 64 columns) took 5.9 ms per step at
 // B = 32, on the main queue.  An embedding gradient is an index_add; what makes it order-dependent is floating-point addition.  So the
 // token rows scatter into two-limb INTEGER accumulators (common.hpp stat_add: trunc(v) and round(frac * 2^44) as int64 atomics --
-// associative, hence the same bits whatever order the wavefronts arrive in), one wavefront per token row like the default kernel, and
-// a second pass decodes the table-shaped accumulator and adds it to the gradient.  ~0.3 ms for both tables.
+// associative, hence the same bits whatever order the wavefronts arrive in), one wavefront per token row, and a second pass decodes
+// the table-shaped accumulator and adds it to the gradient.  ~0.3 ms for both tables.
 __global__ __launch_bounds__(256) void embed_bwd_limb_scatter_kernel(const float* __restrict__ dx, const int64_t* __restrict__ positions,
                                                                     const int* __restrict__ sizes, int B, int N, int n, int F, int D,
                                                                     int rows, int kind, double* __restrict__ acc, int64_t limb) {
@@ -776,11 +714,10 @@ __global__ __launch_bounds__(CLS_W * 64) void attn_cls_bwd_kernel(const float* _
 // ---------------------------------------------------------------------------------------- space attention backward on the matrix cores
 // One wavefront per (b, h, frame), same transposed formulation as attn_space_fwd_mfma_kernel (tsf_fwd.hip): every product is
 // arranged so that its B operand is an accumulator of the previous product used in place, and its A operand is read from global
-// memory either by rows (128 contiguous bytes per lane) or by columns (coalesced across lanes).  No LDS except 512 B of
-// per-query softmax statistics handed from phase A to phase B.
+// memory either by rows (128 contiguous bytes per lane) or by columns (coalesced across lanes).
 //   phase A, lane = query:  S^T = K (sQ)^T, dP^T = V dO^T  ->  P^T, delta, dS^T (all in-lane)  ->  dQ^T = K^T dS^T
-//   phase B, lane = key  :  S = (sQ) K^T,  dP = dO V^T     ->  P, dS (statistics from phase A)  ->  dV^T = dO^T P,  dK^T = (sQ)^T dS
-// 896 v_mfma_f32_32x32x2_f32 per group.  dq is stored; dk / dv are added onto the cls query's contribution written by
+//   phase B, lane = key  :  P, dS (phase A's P^T and dS^T, handed over through LDS)  ->  dV^T = dO^T P,  dK^T = (sQ)^T dS
+// 640 v_mfma_f32_32x32x2_f32 per group.  dq is stored; dk / dv are added onto the cls query's contribution written by
 // attn_cls_bwd_kernel (read-modify-write: a patch key belongs to exactly one group; fp32 atomics for the shared cls key).
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -792,20 +729,18 @@ __device__ __forceinline__ void load_row32(const float* __restrict__ p, float (&
   }
 }
 
-// XP (round 6, default): phase B does not recompute P and dS (256 of the 896 MFMAs, plus the row loads of Q and dO) -- phase A leaves
-// P^T and dS^T in LDS as [key][query] with a 65-float row stride (33 KB per wavefront, dynamic LDS: the block's four wavefronts take
-// 133 KB, one block per CU as before), written along rows and read back along columns, both conflict-free.  640 MFMAs per group.
+// Phase B does not recompute P and dS (256 more MFMAs, plus the row loads of Q and dO): phase A leaves P^T and dS^T in LDS as
+// [key][query] with a 65-float row stride (33 KB per wavefront, dynamic LDS: the block's four wavefronts take 133 KB, one block per
+// CU), written along rows and read back along columns, both conflict-free.
 constexpr int XP_LD = 65;
-template <int WPB, bool FACT = false, bool XP = false>
+template <int WPB, bool FACT>
 __global__ __launch_bounds__(WPB * 64) void attn_space_bwd_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                                       float* __restrict__ dqkv, int B, int H, int F, int n,
                                                                       float scale, const PlaneRef dp, const DetLog det) {
-  __shared__ float2 stat_all[XP ? 1 : WPB][64];             // (logsumexp, delta) per query of the wavefront's group
   extern __shared__ __attribute__((aligned(16))) float xp_lds[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int c = lane & 31, hf = lane >> 5;
-  float2* stat = stat_all[XP ? 0 : wave];
-  float* Pm = xp_lds + (XP ? wave * 2 * 64 * XP_LD : 0);    // P^T [key slot][query slot]
+  float* Pm = xp_lds + wave * 2 * 64 * XP_LD;               // P^T [key slot][query slot]
   float* Sm = Pm + 64 * XP_LD;                              // dS^T
   const int N = 1 + F * n, inner = H * DH, ld = 3 * inner;
   const int64_t wid = (int64_t)blockIdx.x * WPB + wave;
@@ -873,22 +808,18 @@ __global__ __launch_bounds__(WPB * 64) void attn_space_bwd_mfma_kernel(const flo
 #pragma unroll
       for (int r = 0; r < 16; ++r) { st[i][r] *= inv; delta = fmaf(st[i][r], dpt[i][r], delta); }
     delta += __shfl_xor(delta, 32);
-    if constexpr (XP) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) Pm[(32 * i + mfma_slot_row(r, hf)) * XP_LD + q] = st[i][r];
-    }
+      for (int r = 0; r < 16; ++r) Pm[(32 * i + mfma_slot_row(r, hf)) * XP_LD + q] = st[i][r];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) st[i][r] *= dpt[i][r] - delta;          // dS^T (zero on padded keys: P^T is zero there)
-    if constexpr (XP) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) Sm[(32 * i + mfma_slot_row(r, hf)) * XP_LD + q] = st[i][r];
-    } else if (hf == 0) stat[q] = make_float2(mx + __logf(sum), delta);
+      for (int r = 0; r < 16; ++r) Sm[(32 * i + mfma_slot_row(r, hf)) * XP_LD + q] = st[i][r];
     f32x16 dq[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -910,7 +841,7 @@ __global__ __launch_bounds__(WPB * 64) void attn_space_bwd_mfma_kernel(const flo
         }
     }
   }
-  __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): the statistics are in LDS
+  __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): P^T and dS^T are in LDS
   __builtin_amdgcn_wave_barrier();
 
   // ---------------------------------------------------------------- phase B: lane = key (32 j + c)
@@ -918,24 +849,6 @@ __global__ __launch_bounds__(WPB * 64) void attn_space_bwd_mfma_kernel(const flo
   for (int j = 0; j < 2; ++j) {
     const int key = 32 * j + c;
     f32x16 pp[2], ds[2];                      // P and dS tiles [query tile]
-    if constexpr (!XP) {
-      float kb[32], vb[32];
-      load_row32(base + (int64_t)tok_k(key) * ld + inner + hf * 32, kb, 1.0f);
-      load_row32(base + (int64_t)tok_k(key) * ld + 2 * inner + hf * 32, vb, 1.0f);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        float qa[32], da[32];
-        load_row32(base + (int64_t)tok_q(32 * i + c) * ld + hf * 32, qa, scale);
-        load_row32(dobase + (int64_t)tok_q(32 * i + c) * inner + hf * 32, da, 1.0f);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { pp[i][r] = 0.f; ds[i][r] = 0.f; }
-#pragma unroll
-        for (int ks = 0; ks < 32; ++ks) {
-          pp[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[ks], kb[ks], pp[i], 0, 0, 0);
-          ds[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(da[ks], vb[ks], ds[i], 0, 0, 0);
-        }
-      }
-    }
     // dO and scaled Q by columns, in the query order the P / dS accumulators are consumed in
     float dc[2][32], qc[2][32];
 #pragma unroll
@@ -951,16 +864,9 @@ __global__ __launch_bounds__(WPB * 64) void attn_space_bwd_mfma_kernel(const flo
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int q = 32 * i + mfma_slot_row(r, hf);
-        if constexpr (XP) {                   // phase A's P^T / dS^T, read along a column (rows of padded keys hold zeros; padded
-          const bool ok = q < n;              // query slots hold copies of the last query: masked here)
-          pp[i][r] = ok ? Pm[key * XP_LD + q] : 0.f;
-          ds[i][r] = ok ? Sm[key * XP_LD + q] : 0.f;
-        } else {
-          const float2 sd = stat[q];
-          const float p = (q < n && key <= n) ? __expf(pp[i][r] - sd.x) : 0.f;
-          ds[i][r] = p * (ds[i][r] - sd.y);
-          pp[i][r] = p;
-        }
+        const bool ok = q < n;                // phase A's P^T / dS^T, read along a column (rows of padded keys hold zeros; padded
+        pp[i][r] = ok ? Pm[key * XP_LD + q] : 0.f;      // query slots hold copies of the last query: masked here)
+        ds[i][r] = ok ? Sm[key * XP_LD + q] : 0.f;
       }
     f32x16 dv[2], dk[2];
 #pragma unroll
@@ -1032,8 +938,8 @@ __global__ __launch_bounds__(WPB * 64) void attn_space_bwd_mfma_kernel(const flo
 //            by key tile (K by columns, 16 steps each); the query's (row max, 1 / sum, delta) go to 1.5 KB of LDS per wavefront
 //   phase B, per key tile, lane = key:  for every query tile recompute S and dP (the same products in the same order as phase A:
 //            the same bits), P = exp(S - max) / sum and dS from the statistics, and accumulate dV^T += dO^T P, dK^T += (sQ)^T dS
-// A 128 x 128 P^T and dS^T do not fit 160 KB of LDS four wavefronts to a block, hence the recomputation (the non-XP form of the 2 x 2
-// kernel); 64 NK + 64 MFMAs per query tile in phase A and 128 per (key tile, query tile) in phase B.
+// A 128 x 128 P^T and dS^T do not fit 160 KB of LDS four wavefronts to a block, hence the recomputation (the 2 x 2 kernel hands them
+// from phase A to phase B through LDS instead); 64 NK + 64 MFMAs per query tile in phase A and 128 per (key tile, query tile) in phase B.
 template <int WPB, int NK, bool FACT>
 __global__ __launch_bounds__(WPB * 64) void attn_space_bwd_mfma_wide_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                                            float* __restrict__ dqkv, int B, int H, int F, int n,
@@ -1251,16 +1157,16 @@ __global__ __launch_bounds__(WPB * 64) void attn_space_bwd_mfma_wide_kernel(cons
 }
 
 // ---------------------------------------------------------------------------------------- attention backward: patch queries
-// Same decomposition as the forward kernel (one lane per query; MODE 0 time / 1 space).
+// Time attention at F = 32, same decomposition as the forward kernel (attn_patch_fwd_kernel: one lane per query).
 // pass 1 (lane = query i): s_ij, p_ij, dP_ij = dO_i.v_j, delta_i, dS_ij = p_ij(dP_ij - delta_i), dq_i = scale*sum_j dS_ij k_j
 // pass 2 (lane = key  j): dk_j = sum_i dS_ij (scale q_i),  dv_j = sum_i p_ij dO_i   -- roles transposed through LDS
 // Per-wavefront LDS: tile A [ROWS][STRIDE] (K, later Q.scale), tile B [ROWS][STRIDE] (V, later dO), P and dS [64][SP].
-template <int MODE, int NKEYS, int PPW, int STRIDE, int WPB>
+template <int NKEYS, int PPW, int STRIDE, int WPB>
 __global__ __launch_bounds__(WPB * 64) void attn_patch_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                                  float* __restrict__ dqkv, const uint8_t* __restrict__ mask,
                                                                  const uint8_t* __restrict__ ident, int B, int H, int F, int n,
                                                                  float scale, const PlaneRef dp, const DetLog det) {
-  constexpr int ROWS = MODE == 0 ? 1 + PPW * (NKEYS - 1) : NKEYS;
+  constexpr int ROWS = 1 + PPW * (NKEYS - 1);
   constexpr int QROWS = 64;                                  // pass-2 tiles hold one row per query lane
   constexpr int TROWS = ROWS > QROWS ? ROWS : QROWS;
   constexpr int SP = (NKEYS % 2 == 0) ? NKEYS + 1 : NKEYS;   // odd stride: conflict-free writer lanes
@@ -1275,7 +1181,7 @@ __global__ __launch_bounds__(WPB * 64) void attn_patch_bwd_kernel(const float* _
   const int N = 1 + F * n;
   const int inner = H * DH;
   const int ld = 3 * inner;
-  const int chunks = MODE == 0 ? (n + PPW - 1) / PPW : F;
+  const int chunks = (n + PPW - 1) / PPW;
   const int64_t wid = (int64_t)blockIdx.x * WPB + wave;
   if (wid >= (int64_t)B * H * chunks) return;
   const int c = (int)(wid % chunks);
@@ -1285,25 +1191,20 @@ __global__ __launch_bounds__(WPB * 64) void attn_patch_bwd_kernel(const float* _
   float* dbase = dqkv + (int64_t)b * N * ld + h * DH;
   const float* dob = dout + (int64_t)b * N * inner + h * DH;
 
-  int qtok = -1, pl = 0, fq = 0;
-  if (MODE == 0) {
-    pl = lane / (NKEYS - 1); fq = lane % (NKEYS - 1);
+  int qtok = -1, pl = lane / (NKEYS - 1);
+  const int fq = lane % (NKEYS - 1);
+  {
     const int p = c * PPW + pl;
     if (pl < PPW && p < n) qtok = 1 + fq * n + p;
     if (pl >= PPW) pl = 0;
-  } else {
-    if (lane < n) qtok = 1 + c * n + lane;
   }
-  const int row1 = MODE == 0 ? 1 + pl * (NKEYS - 1) : 1;
+  const int row1 = 1 + pl * (NKEYS - 1);
 
   auto row_token = [&](int r) -> int {
     if (r == 0) return 0;
-    if (MODE == 0) {
-      const int pl2 = (r - 1) / (NKEYS - 1), f2 = (r - 1) % (NKEYS - 1);
-      const int p = c * PPW + pl2;
-      return p < n ? 1 + f2 * n + p : -1;
-    }
-    return 1 + c * n + (r - 1);
+    const int pl2 = (r - 1) / (NKEYS - 1), f2 = (r - 1) % (NKEYS - 1);
+    const int p = c * PPW + pl2;
+    return p < n ? 1 + f2 * n + p : -1;
   };
   auto stage = [&](float* tile, int which) {
     for (int r0 = 0; r0 < ROWS; r0 += 4) {
@@ -1348,7 +1249,7 @@ __global__ __launch_bounds__(WPB * 64) void attn_patch_bwd_kernel(const float* _
       a1 = fmaf(q[8 * i + 6], k1.z, a1); a1 = fmaf(q[8 * i + 7], k1.w, a1);
     }
     float a = a0 + a1;
-    if (MODE == 0 && j > 0) {
+    if (j > 0) {
       const bool ok = mask[b * F + (j - 1)] && ident[(b * F + fq) * F + (j - 1)];
       if (!ok) a = -FLT_MAX;
     }
@@ -1435,10 +1336,10 @@ __global__ __launch_bounds__(WPB * 64) void attn_patch_bwd_kernel(const float* _
     float dk[DH], dv[DH];
 #pragma unroll
     for (int i = 0; i < DH; ++i) { dk[i] = 0.f; dv[i] = 0.f; }
-    // queries that see my token as a key: time -> the F lanes of my patch group; space -> all n lanes
-    const int i0 = MODE == 0 ? pl * (NKEYS - 1) : 0;
-    const int cnt = MODE == 0 ? (NKEYS - 1) : n;
-    const int jme = MODE == 0 ? 1 + fq : 1 + lane;           // my key index inside those queries' score rows
+    // queries that see my token as a key: the F lanes of my patch group
+    const int i0 = pl * (NKEYS - 1);
+    constexpr int cnt = NKEYS - 1;
+    const int jme = 1 + fq;                                  // my key index inside those queries' score rows
 #pragma unroll 2
     for (int t = 0; t < cnt; ++t) {
       const int iq = i0 + t;
@@ -1711,16 +1612,16 @@ __global__ __launch_bounds__(256) void attn_bwd_cls_planes_kernel(const float* _
   }
 }
 
-template <int MODE, int NKEYS, int PPW, int STRIDE, int WPB>
+template <int NKEYS, int PPW, int STRIDE, int WPB>
 int launch_patch_bwd(const float* qkv, const float* dout, float* dqkv, const uint8_t* mask, const uint8_t* ident, int B, int H,
                      int F, int n, float scale, const PlaneRef& dp, const DetLog& det, hipStream_t s) {
-  constexpr int ROWS = MODE == 0 ? 1 + PPW * (NKEYS - 1) : NKEYS;
+  constexpr int ROWS = 1 + PPW * (NKEYS - 1);
   constexpr int TROWS = ROWS > 64 ? ROWS : 64;
   constexpr int SP = (NKEYS % 2 == 0) ? NKEYS + 1 : NKEYS;
-  const int chunks = MODE == 0 ? (n + PPW - 1) / PPW : F;
+  const int chunks = (n + PPW - 1) / PPW;
   const int64_t waves = (int64_t)B * H * chunks;
   const size_t lds = (size_t)WPB * (2 * TROWS * STRIDE + 2 * 64 * SP) * sizeof(float);
-  auto k = attn_patch_bwd_kernel<MODE, NKEYS, PPW, STRIDE, WPB>;
+  auto k = attn_patch_bwd_kernel<NKEYS, PPW, STRIDE, WPB>;
   if (lds > 48 * 1024) {
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds);
     if (e != hipSuccess) return fail(MT_ERR_LAUNCH, "mt_attn_bwd: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
@@ -1739,8 +1640,7 @@ extern "C" int mt_layernorm_bwd(const float* dy, const float* x, const float* st
   if (dim <= 0 || (dim & 3) || dim > 1024) return fail(MT_ERR_ARG, "mt_layernorm_bwd: dim %d unsupported", dim);
   if (rows <= 0) return 0;
   int blocks = (rows + 3) / 4;
-  static const int cap = env_int("MT_LN_BWD_BLOCKS", 256);     // tuning knob
-  if (blocks > cap) blocks = cap;
+  if (blocks > 256) blocks = 256;
   DetScope det((hipStream_t)stream, 3, blocks, dim, true, true);     // deterministic mode: the three column sums by block order
   if (dim <= 512)
     hipLaunchKernelGGL(layernorm_bwd_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, x, stats, gamma, dx, dgamma, dbeta,
@@ -1766,11 +1666,8 @@ extern "C" int mt_layernorm_bwd_rows(const float* dy, const float* x, const floa
   const int rp = (rows + 31) & ~31;
   const PlaneRef dxp{reinterpret_cast<__bf16*>(dx_planes), (int64_t)rp * dim, dim >> 4, rp};
   const int blocks = ln_rows_blocks(rows);
-  static const int keep = env_int("MT_LN_ROWS_KEEP", 1);
-  if (dim <= 512 && keep)
+  if (dim <= 512)
     hipLaunchKernelGGL(layernorm_bwd_rows_kernel2k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, x, stats, gamma, dx, dx_in, rows, dim, dxp);
-  else if (dim <= 512)
-    hipLaunchKernelGGL(layernorm_bwd_rows_kernel2, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, x, stats, gamma, dx, dx_in, rows, dim, dxp);
   else
     hipLaunchKernelGGL(layernorm_bwd_rows_kernel4, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, x, stats, gamma, dx, dx_in, rows, dim, dxp);
   return check_launch("mt_layernorm_bwd_rows");
@@ -1778,8 +1675,7 @@ extern "C" int mt_layernorm_bwd_rows(const float* dy, const float* x, const floa
 
 static int ln_rows_blocks(int rows) {
   int blocks = (rows + 3) / 4;
-  static const int cap = env_int("MT_LN_ROWS_BLOCKS", 1024);    // tuning knob
-  if (blocks > cap) blocks = cap;
+  if (blocks > 1024) blocks = 1024;
   return blocks < 1 ? 1 : blocks;
 }
 
@@ -1862,13 +1758,11 @@ extern "C" int mt_embed_bwd(const float* dx, float* dcls, float* dpos_emb, float
   const int N = 1 + F * n;
   if (det_enabled()) {
     hipStream_t s = (hipStream_t)stream;
-    static const bool walk = env_set("MT_DET_EMBED_WALK");        // A/B aid: round 4's run walk for all three gradients
     const int srows = dsize_emb ? size_rows : 1;
-    // cls token: B ordered adds per column (kind 0 of the walk kernel); the tables: integer-limb scatter + decode
-    hipLaunchKernelGGL(embed_bwd_det_kernel, dim3((dim + 63) / 64, walk ? 3 : 1), dim3(64), 0, s, dx, dcls,
-                       dpos_emb, dsize_emb, positions, sizes, B, N, n, F, dim, pos_rows, srows);
+    // cls token: B ordered adds per column; the tables: integer-limb scatter + decode
+    hipLaunchKernelGGL(embed_bwd_det_kernel, dim3((dim + 63) / 64), dim3(64), 0, s, dx, dcls, B, N, dim);
     int rc = check_launch("mt_embed_bwd(deterministic)");
-    if (rc || walk) return rc;
+    if (rc) return rc;
     for (int kind = 1; kind <= 2; ++kind) {
       float* dst = kind == 1 ? dpos_emb : dsize_emb;
       if (!dst) continue;
@@ -1887,13 +1781,8 @@ extern "C" int mt_embed_bwd(const float* dx, float* dcls, float* dpos_emb, float
     }
     return 0;
   }
-  static const bool rows_form = env_set("MT_EMBED_BWD_ROWS");        // A/B aid: the row-per-wavefront kernel
-  if (rows_form || F * n + 1 != N)
-    hipLaunchKernelGGL(embed_bwd_kernel, dim3((B * N + 3) / 4), dim3(256), 0, (hipStream_t)stream, dx, dcls, dpos_emb, dsize_emb,
-                       positions, sizes, B, N, n, F, dim, pos_rows, dsize_emb ? size_rows : 1);
-  else
-    hipLaunchKernelGGL(embed_bwd_slots_kernel, dim3(B * F), dim3(256), 0, (hipStream_t)stream, dx, dcls, dpos_emb, dsize_emb,
-                       positions, sizes, B, N, n, F, dim, pos_rows, dsize_emb ? size_rows : 1);
+  hipLaunchKernelGGL(embed_bwd_slots_kernel, dim3(B * F), dim3(256), 0, (hipStream_t)stream, dx, dcls, dpos_emb, dsize_emb,
+                     positions, sizes, B, N, n, F, dim, pos_rows, dsize_emb ? size_rows : 1);
   return check_launch("mt_embed_bwd");
 }
 
@@ -1907,57 +1796,41 @@ extern "C" int mt_attn_bwd(const float* qkv, const float* dout, float* dqkv, con
   const int N = 1 + F * n;
   const int rp = (B * N + 31) & ~31, ld = 3 * H * DH;
   const PlaneRef dp{reinterpret_cast<__bf16*>(dqkv_planes), (int64_t)rp * ld, ld / 16, rp};
-  static const bool time_old = env_set("MT_ATTN_TIME_OLD");    // A/B aid: the 7-patches-per-wavefront kernel
-  static const bool valu = env_set("MT_ATTN_VALU");            // A/B aid: the one-lane-per-query space kernel
-  if (mode == 1 && valu && n != 49) return fail(MT_ERR_UNSUPPORTED, "mt_attn_bwd: MT_ATTN_VALU holds num-patches 49 only (got %d)", n);
-  static const bool fact_on = env_int("MT_ATTN_CLS_FACT", 1) != 0;
   // with plane output the fp32 dqkv is working memory: the cls query's contribution to the patch keys crosses to the patch kernel as two
   // scalars per key and head (kernels that understand it: the MFMA space kernel, the one-patch-per-wavefront time kernel)
   // The scalars park in 2 H ceil(N / inner) of the clip's own N - 1 patch rows (cls_fact_off): a clip with fewer patch rows than that
   // (few patches, many heads) takes the full-row form, or the scalars would land in the next clip and past the buffer.
   const bool fact_fits = (int64_t)2 * H * ((N + H * DH - 1) / (H * DH)) <= N - 1;
-  const bool fact = fact_on && fact_fits && dqkv_planes && ((mode == 1 && !valu) || (mode == 0 && !time_old && (F == 8 || F == 16)));
+  const bool fact = fact_fits && dqkv_planes && (mode == 1 || (mode == 0 && (F == 8 || F == 16)));
   hipLaunchKernelGGL(attn_cls_bwd_kernel, dim3(B * H), dim3(CLS_W * 64), (2 * N + CLS_W + 4 + CLS_W * 64) * sizeof(float), s, qkv, dout, dqkv, mask, B, H, F, n, scale, fact ? 1 : 0);
   int rc = check_launch("mt_attn_bwd(cls)");
   if (rc || mode == 2) return rc;                 // mode 2: the cls query's adjoint only (dk / dv of every key, dq of the cls row)
   // deterministic mode: the cls key's dk / dv (one row per (b, head), shared by every frame / patch group) go through a log with one
   // rank per group of the launched kernel, and are added to the cls kernel's values in rank order (det.hpp)
-  const int det_ranks = mode == 1 ? F : (!time_old && (F == 8 || F == 16) ? n : (F == 8 ? (n + 6) / 7 : (F == 16 ? (n + 3) / 4 : (n + 1) / 2)));
+  const int det_ranks = mode == 1 ? F : (F == 8 || F == 16) ? n : (n + 1) / 2;
   DetScope det(s, 2 * B * H, det_ranks, DH);
   if (mode == 1) {
-    if (valu) rc = launch_patch_bwd<1, 50, 1, 64, 2>(qkv, dout, dqkv, mask, ident, B, H, F, n, scale, dp, det.log, s);
-    else {
-      const int64_t waves = (int64_t)B * H * F;
-      static const bool xp = env_int("MT_ATTN_SPACE_XP", 1) != 0;    // 0: phase B recomputes P / dS (round 5)
-      const dim3 grid((unsigned)((waves + 3) / 4));
-      // cls + n keys: up to 64 fit the 2 x 2 tiles; 65..96 take three key tiles, 97..101 four, with the queries walked in tiles
-      if (n + 1 > 96) {
-        if (fact) hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 4, true>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
-        else hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 4, false>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
-      } else if (n + 1 > 64) {
-        if (fact) hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 3, true>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
-        else hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 3, false>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
-      } else if (xp) {
-        constexpr size_t lds = (size_t)4 * 2 * 64 * XP_LD * sizeof(float);
-        auto k = fact ? attn_space_bwd_mfma_kernel<4, true, true> : attn_space_bwd_mfma_kernel<4, false, true>;
-        if (ensure_dynamic_lds((const void*)k, lds) != hipSuccess) return fail(MT_ERR_LAUNCH, "mt_attn_bwd(space): %zu bytes of LDS refused", lds);
-        hipLaunchKernelGGL(k, grid, dim3(256), lds, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
-      } else if (fact) hipLaunchKernelGGL((attn_space_bwd_mfma_kernel<4, true, false>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
-      else hipLaunchKernelGGL((attn_space_bwd_mfma_kernel<4, false, false>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
-      rc = check_launch("mt_attn_bwd(space, mfma)");
+    const int64_t waves = (int64_t)B * H * F;
+    const dim3 grid((unsigned)((waves + 3) / 4));
+    // cls + n keys: up to 64 fit the 2 x 2 tiles; 65..96 take three key tiles, 97..101 four, with the queries walked in tiles
+    if (n + 1 > 96) {
+      if (fact) hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 4, true>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
+      else hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 4, false>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
+    } else if (n + 1 > 64) {
+      if (fact) hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 3, true>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
+      else hipLaunchKernelGGL((attn_space_bwd_mfma_wide_kernel<4, 3, false>), grid, dim3(256), 0, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
+    } else {
+      constexpr size_t lds = (size_t)4 * 2 * 64 * XP_LD * sizeof(float);
+      auto k = fact ? attn_space_bwd_mfma_kernel<4, true> : attn_space_bwd_mfma_kernel<4, false>;
+      if (ensure_dynamic_lds((const void*)k, lds) != hipSuccess) return fail(MT_ERR_LAUNCH, "mt_attn_bwd(space): %zu bytes of LDS refused", lds);
+      hipLaunchKernelGGL(k, grid, dim3(256), lds, s, qkv, dout, dqkv, B, H, F, n, scale, dp, det.log);
     }
-  } else if (!time_old) {
+    rc = check_launch("mt_attn_bwd(space, mfma)");
+  } else {
     switch (F) {
       case 8: rc = launch_time_bwd<8, 4>(qkv, dout, dqkv, mask, ident, B, H, n, scale, dp, fact, det.log, s); break;
       case 16: rc = launch_time_bwd<16, 2>(qkv, dout, dqkv, mask, ident, B, H, n, scale, dp, fact, det.log, s); break;
-      case 32: rc = launch_patch_bwd<0, 33, 2, 68, 2>(qkv, dout, dqkv, mask, ident, B, H, F, n, scale, dp, det.log, s); break;   // (130 row registers: spills)
-      default: return fail(MT_ERR_UNSUPPORTED, "mt_attn_bwd: num-frames %d unsupported (8/16/32)", F);
-    }
-  } else {
-    switch (F) {
-      case 8: rc = launch_patch_bwd<0, 9, 7, 68, 2>(qkv, dout, dqkv, mask, ident, B, H, F, n, scale, dp, det.log, s); break;
-      case 16: rc = launch_patch_bwd<0, 17, 4, 68, 2>(qkv, dout, dqkv, mask, ident, B, H, F, n, scale, dp, det.log, s); break;
-      case 32: rc = launch_patch_bwd<0, 33, 2, 68, 2>(qkv, dout, dqkv, mask, ident, B, H, F, n, scale, dp, det.log, s); break;
+      case 32: rc = launch_patch_bwd<33, 2, 68, 2>(qkv, dout, dqkv, mask, ident, B, H, F, n, scale, dp, det.log, s); break;   // (130 row registers: spills)
       default: return fail(MT_ERR_UNSUPPORTED, "mt_attn_bwd: num-frames %d unsupported (8/16/32)", F);
     }
   }

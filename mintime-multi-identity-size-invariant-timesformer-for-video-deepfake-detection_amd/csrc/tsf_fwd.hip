@@ -115,16 +115,15 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(float* __restrict__ x, c
 }
 
 // ---------------------------------------------------------------------------------------- attention: patch queries
-// MODE 0 = time  : group = (b,h,patch p): F queries (tokens 1+f*n+p), keys = cls + the same F tokens, identity mask
-// MODE 1 = space : group = (b,h,frame f): n queries (tokens 1+f*n+p), keys = cls + the same n tokens, no mask
-// One lane per query. NKEYS = keys per query (F+1 or n+1).  PPW = patches per wavefront in time mode.
+// Time attention at F = 32 (launch_time_fwd holds F = 8 / 16): group = (b,h,patch p): F queries (tokens 1+f*n+p), keys = cls + the
+// same F tokens, identity mask.  One lane per query.  NKEYS = keys per query (F+1).  PPW = patches per wavefront.
 // Per wavefront LDS: a [ROWS][STRIDE] K tile (re-used for V) + a [NKEYS][64] score tile (lane-contiguous).
-template <int MODE, int NKEYS, int PPW, int STRIDE, int WPB>
+template <int NKEYS, int PPW, int STRIDE, int WPB>
 __global__ __launch_bounds__(WPB * 64) void attn_patch_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                  const uint8_t* __restrict__ mask,
                                                                  const uint8_t* __restrict__ ident,
                                                                  int B, int H, int F, int n, float scale, const PlaneRef op) {
-  constexpr int ROWS = MODE == 0 ? 1 + PPW * (NKEYS - 1) : NKEYS;
+  constexpr int ROWS = 1 + PPW * (NKEYS - 1);
   constexpr int WAVE_LDS = ROWS * STRIDE + NKEYS * 64;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -134,7 +133,7 @@ __global__ __launch_bounds__(WPB * 64) void attn_patch_fwd_kernel(const float* _
   const int N = 1 + F * n;
   const int inner = H * DH;
   const int ld = 3 * inner;
-  const int chunks = MODE == 0 ? (n + PPW - 1) / PPW : F;
+  const int chunks = (n + PPW - 1) / PPW;
   const int64_t wid = (int64_t)blockIdx.x * WPB + wave;
   if (wid >= (int64_t)B * H * chunks) return;       // wave-uniform
   const int c = (int)(wid % chunks);
@@ -143,16 +142,14 @@ __global__ __launch_bounds__(WPB * 64) void attn_patch_fwd_kernel(const float* _
   const float* base = qkv + (int64_t)b * N * ld + h * DH;
 
   // my query
-  int qtok = -1, pl = 0, fq = 0;
-  if (MODE == 0) {
-    pl = lane / (NKEYS - 1); fq = lane % (NKEYS - 1);
+  int qtok = -1, pl = lane / (NKEYS - 1);
+  const int fq = lane % (NKEYS - 1);
+  {
     const int p = c * PPW + pl;
     if (pl < PPW && p < n) qtok = 1 + fq * n + p;
     if (pl >= PPW) pl = 0;   // idle lanes must still address rows inside this wavefront's LDS slice
-  } else {
-    if (lane < n) qtok = 1 + c * n + lane;
   }
-  const int row1 = MODE == 0 ? 1 + pl * (NKEYS - 1) : 1;   // LDS row of my key j = 1
+  const int row1 = 1 + pl * (NKEYS - 1);   // LDS row of my key j = 1
 
   auto stage = [&](int which) {   // which: 1 = K, 2 = V
     for (int r0 = 0; r0 < ROWS; r0 += 4) {
@@ -160,13 +157,9 @@ __global__ __launch_bounds__(WPB * 64) void attn_patch_fwd_kernel(const float* _
       if (r < ROWS) {
         int tok = 0;
         if (r > 0) {
-          if (MODE == 0) {
-            const int pl2 = (r - 1) / (NKEYS - 1), f2 = (r - 1) % (NKEYS - 1);
-            const int p = c * PPW + pl2;
-            tok = p < n ? 1 + f2 * n + p : -1;
-          } else {
-            tok = 1 + c * n + (r - 1);
-          }
+          const int pl2 = (r - 1) / (NKEYS - 1), f2 = (r - 1) % (NKEYS - 1);
+          const int p = c * PPW + pl2;
+          tok = p < n ? 1 + f2 * n + p : -1;
         }
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (tok >= 0) v = *reinterpret_cast<const float4*>(base + (int64_t)tok * ld + which * inner + c4 * 4);
@@ -202,7 +195,7 @@ __global__ __launch_bounds__(WPB * 64) void attn_patch_fwd_kernel(const float* _
       a1 = fmaf(q[8 * i + 6], k1.z, a1); a1 = fmaf(q[8 * i + 7], k1.w, a1);
     }
     float a = a0 + a1;
-    if (MODE == 0 && j > 0) {
+    if (j > 0) {
       const bool ok = mask[b * F + (j - 1)] && ident[(b * F + fq) * F + (j - 1)];
       if (!ok) a = -FLT_MAX;                      // masked_fill_(~mask, -finfo.max)  (:82-85)
     }
@@ -735,14 +728,14 @@ extern "C" int mt_embed_fwd(float* x, const float* cls, const float* pos_emb, co
 }
 
 namespace {
-template <int MODE, int NKEYS, int PPW, int STRIDE, int WPB>
+template <int NKEYS, int PPW, int STRIDE, int WPB>
 int launch_patch(const float* qkv, float* out, const uint8_t* mask, const uint8_t* ident, int B, int H, int F, int n,
                  float scale, const PlaneRef& op, hipStream_t s) {
-  constexpr int ROWS = MODE == 0 ? 1 + PPW * (NKEYS - 1) : NKEYS;
-  const int chunks = MODE == 0 ? (n + PPW - 1) / PPW : F;
+  constexpr int ROWS = 1 + PPW * (NKEYS - 1);
+  const int chunks = (n + PPW - 1) / PPW;
   const int64_t waves = (int64_t)B * H * chunks;
   const size_t lds = (size_t)WPB * (ROWS * STRIDE + NKEYS * 64) * sizeof(float);
-  auto k = attn_patch_fwd_kernel<MODE, NKEYS, PPW, STRIDE, WPB>;
+  auto k = attn_patch_fwd_kernel<NKEYS, PPW, STRIDE, WPB>;
   if (lds > 48 * 1024) {
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds);
     if (e != hipSuccess) return fail(MT_ERR_LAUNCH, "mt_attn_fwd: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
@@ -773,8 +766,6 @@ extern "C" int mt_attn_fwd(const float* qkv, float* out, float* cls_att, const u
   if (out_planes && (mode == 2 || ((uintptr_t)out_planes & 15))) return fail(MT_ERR_ARG, "mt_attn_fwd: plane output needs mode 0 / 1 and 16-byte alignment");
   if (mode == 0 && (!mask || !ident)) return fail(MT_ERR_ARG, "mt_attn_fwd: time attention needs mask and identities_mask");
   if (n < 1 || n > 100) return fail(MT_ERR_UNSUPPORTED, "mt_attn_fwd: num-patches %d unsupported (1..100)", n);
-  static const bool valu = env_set("MT_ATTN_VALU");       // A/B aid: the one-lane-per-query space kernel (built for 50 keys)
-  if (mode == 1 && valu && n != 49) return fail(MT_ERR_UNSUPPORTED, "mt_attn_fwd: MT_ATTN_VALU holds num-patches 49 only (got %d)", n);
   hipStream_t s = (hipStream_t)stream;
   const int N = 1 + F * n;
   const int rp = (B * N + 31) & ~31;
@@ -783,7 +774,6 @@ extern "C" int mt_attn_fwd(const float* qkv, float* out, float* cls_att, const u
   int rc = check_launch("mt_attn_fwd(cls)");
   if (rc || mode == 2) return rc;                 // mode 2: the cls query only (out row 0 of every clip; the patch rows are not written)
   if (mode == 1) {
-    if (valu) return launch_patch<1, 50, 1, 64, 2>(qkv, out, mask, ident, B, H, F, n, scale, op, s);
     const int64_t waves = (int64_t)B * H * F;
     // cls + n keys: up to 64 fit the 2 x 2 tiles; 65..96 take three key tiles, 97..101 four, with the queries walked in tiles
     if (n + 1 > 96) hipLaunchKernelGGL((attn_space_fwd_mfma_wide_kernel<4, 4>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, qkv, out, B, H, F, n, scale, op);
@@ -791,17 +781,10 @@ extern "C" int mt_attn_fwd(const float* qkv, float* out, float* cls_att, const u
     else hipLaunchKernelGGL(attn_space_fwd_mfma_kernel<4>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, qkv, out, B, H, F, n, scale, op);
     return check_launch("mt_attn_fwd(space, mfma)");
   }
-  static const bool time_old = env_set("MT_ATTN_TIME_OLD");    // A/B aid: the 7-patches-per-wavefront kernel
-  if (!time_old) {
-    switch (F) {
-      case 8: return launch_time_fwd<8, 4>(qkv, out, mask, ident, B, H, n, scale, op, s);
-      case 16: return launch_time_fwd<16, 2>(qkv, out, mask, ident, B, H, n, scale, op, s);
-    }
-  }
   switch (F) {
-    case 8: return launch_patch<0, 9, 7, 68, 4>(qkv, out, mask, ident, B, H, F, n, scale, op, s);
-    case 16: return launch_patch<0, 17, 4, 68, 4>(qkv, out, mask, ident, B, H, F, n, scale, op, s);
-    case 32: return launch_patch<0, 33, 2, 68, 4>(qkv, out, mask, ident, B, H, F, n, scale, op, s);
+    case 8: return launch_time_fwd<8, 4>(qkv, out, mask, ident, B, H, n, scale, op, s);
+    case 16: return launch_time_fwd<16, 2>(qkv, out, mask, ident, B, H, n, scale, op, s);
+    case 32: return launch_patch<33, 2, 68, 4>(qkv, out, mask, ident, B, H, F, n, scale, op, s);
   }
   return fail(MT_ERR_UNSUPPORTED, "mt_attn_fwd: num-frames %d unsupported (8/16/32, reference train.py:101)", F);
 }

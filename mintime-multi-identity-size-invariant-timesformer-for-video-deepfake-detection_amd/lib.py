@@ -608,26 +608,13 @@ def grads_ready(model, params, flat):
         hook(params, flat)
 
 
-def _low_priority_stream(device, cu_mask_words=None):
+def _low_priority_stream(device):
     """The weight-gradient stream at the LOWEST hardware queue priority: its kernels fill the CUs the critical path leaves idle
     instead of taking CUs from it (in-step trace: with equal priorities the main queue's LayerNorm-backward launches stretched
     2x next to the three-blocks-per-CU weight-gradient GEMMs).  torch only exposes normal / high, so the stream is created through
     the HIP runtime and wrapped.  MT_SIDE_PRIORITY=normal keeps torch's default."""
     if os.environ.get("MT_SIDE_PRIORITY", "low") != "low":
         return torch.cuda.Stream(device=device)
-    if cu_mask_words:
-        # experiment: confine the stream's kernels to a subset of the CUs (hipExtStreamCreateWithCUMask; 32 CUs per word)
-        try:
-            hip = C.CDLL("libamdhip64.so")
-            idx = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
-            arr = (C.c_uint32 * len(cu_mask_words))(*cu_mask_words)
-            handle = C.c_void_p()
-            with torch.cuda.device(idx):
-                rc = hip.hipExtStreamCreateWithCUMask(C.byref(handle), C.c_uint32(len(cu_mask_words)), arr)
-            if rc == 0:
-                return torch.cuda.ExternalStream(handle.value, device=torch.device("cuda", idx))
-        except (OSError, AttributeError):
-            pass
     try:
         hip = C.CDLL("libamdhip64.so")
         least, greatest = C.c_int(0), C.c_int(0)
@@ -651,7 +638,7 @@ class SideStream:
 
     _streams = {}
 
-    def __init__(self, device, enabled=True, name="", hold=False):
+    def __init__(self, device, enabled=True, hold=False):
         """hold: instead of record_stream, the tensors a side launch reads are kept alive by this object and dropped in HOST order
         at `release_point()`s, two points behind, after the main stream has been made to wait for the side stream's progress
         up to there.  record_stream hands a block back only once the allocator has seen the side event complete: with the host
@@ -663,10 +650,9 @@ class SideStream:
         self.hold = hold and os.environ.get("MT_SIDE_HOLD", "1") != "0"
         self.held, self.epochs = [], []
         if self.enabled:
-            key = str(device) + name                 # name: a further low-priority stream (deferred weight gradients)
+            key = str(device)
             if key not in SideStream._streams:
-                mask = os.environ.get("MT_LATE_CU_MASK") if name else None      # "ffffffff,ffffffff,0,0,..." (hex words, 32 CUs each)
-                SideStream._streams[key] = _low_priority_stream(device, [int(w, 16) for w in mask.split(",")] if mask else None)
+                SideStream._streams[key] = _low_priority_stream(device)
             self.stream = SideStream._streams[key]
         self.pending = []
 

@@ -1,8 +1,8 @@
 """Reverse launch sequence of the Size-Invariant TimeSformer (analytic backward, not torch autograd over torch ops).
 
 Walks the layers last-to-first on the saved buffers of tsf_engine.tsf_forward:
-    dgemm (NN) for activations, wgrad (TN, split-K + fp32 atomics) for weights, column sums for biases,
-    the attention-core / LayerNorm / embedding / head adjoint kernels of csrc/tsf_bwd.hip.
+    dgemm (NT over the forward's transposed weights, else NN) for activations, wgrad (TN, split-K + fp32 atomics) for weights,
+    column sums for biases, the attention-core / LayerNorm / embedding / head adjoint kernels of csrc/tsf_bwd.hip.
 `dx` is the running gradient of the residual stream and is updated in place.
 """
 import os
@@ -11,15 +11,6 @@ import torch
 
 from . import arch
 from . import lib as L
-
-
-def _zeros_like_param(p):
-    return torch.zeros_like(p, dtype=torch.float32) if p is not None else None
-
-
-def _splits(M):
-    # enough K-splits to fill the chip for the skinny wgrad outputs, chunk kept >= 512 rows
-    return max(1, min(32, M // 512))
 
 
 def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, need_dparams):
@@ -33,7 +24,6 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
     M = B * N
     eps = arch.LN_EPS
     scale = float(dh) ** -0.5
-    sk = _splits(M)
     grads, flat_grads = L.zero_grads(list(params), with_flat=True)
     P = list(params)
     idx = len(P)
@@ -44,20 +34,6 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
         return idx
 
     side = L.SideStream(dev)
-    # Deferred weight gradients (MT_WGRAD_DEFER=1, off by default).  Inside the TimeSformer's reverse walk the weight-gradient GEMMs
-    # (9 ms of matrix work on the side stream) compete with the data-gradient GEMMs of the critical path for the same matrix cores;
-    # the EfficientNet backward that follows is HBM-bound and leaves those cores idle.  With the switch on the 55 launches are only
-    # RECORDED here (their operands kept: per-layer du / dqkv buffers and out-of-place residual-stream gradients instead of buffers
-    # reused in place, ~4 GB of the 288) and issued after the walk on their own low-priority stream, under the extractor's
-    # backward; the main stream joins that stream when the whole autograd pass has finished (engine callback).
-    # MEASURED (profiles/r03_wgrad_schedule_experiments.txt): the TimeSformer backward phase drops 20.5 -> 12.9 ms and the extractor
-    # backward phase grows 17.3 -> 23.6 ms -- the step is unchanged (54.4 ms), also with the late stream confined to half of the
-    # CUs (hipExtStreamCreateWithCUMask) and with its HBM traffic cut by 45 %.  Concurrency only re-distributes a fixed amount of
-    # work; the GPU runs the step at ~1250 W with the shader clock throttled to ~2245 of 2400 MHz.  Hence off: it would only delay
-    # the TimeSformer gradient bucket of a data-parallel run.
-    defer = (os.environ.get("MT_WGRAD_DEFER", "0") != "0" and need_dfeat and side.enabled and M >= 4096
-             and getattr(model, "_grads_ready_hook", None) is None and not torch.cuda.is_current_stream_capturing())
-    deferred = []
     wT = saved.get("wT")                              # transposed weights (tsf_engine.tsf_forward): data gradients in NT form
     if wT is not None and getattr(model, "_wT_cache", {}).get("serial") != saved.get("wT_serial"):
         wT = None                                     # a later forward rewrote the persistent buffers (two graphs alive): the weights
@@ -68,34 +44,12 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
     def colsum(A, lda, rows, cols, out, amap=(0, 0, 0)):
         L.check(lib.mt_colsum(L.ptr(A), lda, L.RowMap(*amap), rows, cols, L.ptr(out), L.stream_ptr()), "mt_colsum")
 
-    # share of a long-K data gradient that is handed to the side stream (see dgrad_skinny); tuned in-step
-    side_share = float(os.environ.get("MT_DGRAD_SIDE_SHARE", "0.25"))
-
-    def dgrad_skinny(dY, Wm, out, K_, WmT=None):
-        """out[M,D] = dY[M,K_] . Wm[K_,D]: only 396 output tiles -> K-slices + fp32 atomics onto a zeroed output when K is long.
-        The step is bound by the main stream's kernel time while the weight-gradient stream has slack (in-step trace: main
-        97 % busy, side 80-90 %), and a split-K sum does not care which stream a slice runs on: the last `side_share` of the
-        contraction goes to the side stream.  Returns the side launch's event (or None); the caller waits for it before `out`
-        is consumed."""
-        if M >= 4096 and K_ >= 1024 and os.environ.get("MT_SKINNY_SPLIT") == "1":
-            out.zero_()
-            splits = 4 if K_ >= 2048 else 3                      # measured optimum with 64x64 tiles
-            k_side = 0
-            if side.enabled and side_share > 0 and K_ >= 2048:
-                k_side = int(K_ * side_share) // 512 * 512
-            k_main = K_ - k_side
-            ev = None
-            if k_side:
-                dY_s, W_s = dY[:, k_main:], Wm[k_main:]
-                ev = side.launch(lambda: L.gemm(L.OP_NN, dY_s, W_s, out, M, D, k_side, K_, D, D, epilogue=L.EPI_ATOMIC,
-                                                split_k=max(1, round(splits * k_side / K_))), reads=(dY, Wm, out))
-            L.gemm(L.OP_NN, dY, Wm, out, M, D, k_main, K_, D, D, epilogue=L.EPI_ATOMIC, split_k=max(1, round(splits * k_main / K_)))
-            return ev
-        if WmT is not None:
-            L.gemm(L.OP_NT, dY, WmT, out, M, D, K_, K_, K_, D)          # WmT = Wm^T [D, K_]
+    def dgrad(dY, Wm, off, out, N_, K_):
+        """out[M, N_] = dY[M, K_] . Wm[K_, N_]: NT over the transposed weight (wT[(li, off)] = Wm^T [N_, K_]) if there is one, else NN."""
+        if wT is not None:
+            L.gemm(L.OP_NT, dY, wT[(li, off)], out, M, N_, K_, K_, K_, N_)
         else:
-            L.gemm(L.OP_NN, dY, Wm, out, M, D, K_, K_, D, D)
-        return None
+            L.gemm(L.OP_NN, dY, Wm, out, M, N_, K_, K_, N_, N_)
 
     def wgrad(A, Bm, out, M_, N_, K_, lda, ldb, ldc, bias_out=None, **kw):
         """dW (+ db) on the side stream: reads A [K_,M_] and Bm [K_,N_], accumulates into zero-filled grads."""
@@ -103,9 +57,6 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
             L.gemm(L.OP_TN, A, Bm, out, M_, N_, K_, lda, ldb, ldc, epilogue=L.EPI_ATOMIC, split_k=0, **kw)
             if bias_out is not None:
                 colsum(A, lda, K_, M_, bias_out, kw.get("a_map", (0, 0, 0)))
-        if defer:
-            deferred.append((run, (A, Bm)))
-            return None
         return side.launch(run, reads=(A, Bm))
 
     def ln_bwd(dxn_, r_, g_, dx_cur, i_g, tgt, skip):
@@ -113,8 +64,8 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
         gradients that read dx_cur are still to come -- into a fresh buffer.  With the weight-gradient stream on, only dx is
         computed on the main stream (mt_layernorm_bwd_rows: 48 VGPRs, no LDS -- it co-resides with the weight-gradient GEMMs
         instead of waiting for their blocks to end); the three column sums are parameter gradients and go to the side stream."""
-        dx_new = torch.empty_like(dx_cur) if ln_oop else dx_cur
-        if ln_split:
+        if ln_oop:
+            dx_new = torch.empty_like(dx_cur)
             x_, st_ = r_["x"], r_["stats"]
             L.check(lib.mt_layernorm_bwd_rows(L.ptr(dxn_), L.ptr(x_), L.ptr(st_), L.ptr(g_), L.ptr(dx_new), L.ptr(dx_cur), M, D, None, st),
                     "mt_layernorm_bwd_rows")
@@ -122,10 +73,9 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
                                                                   L.ptr(grads[i_g + 1]), L.ptr(tgt), skip, M, D, L.stream_ptr()),
                                         "mt_layernorm_bwd_cols"), reads=(dxn_, x_, st_, dx_new))
             return dx_new
-        L.check(lib.mt_layernorm_bwd(L.ptr(dxn_), L.ptr(r_["x"]), L.ptr(r_["stats"]), L.ptr(g_), L.ptr(dx_new), L.ptr(grads[i_g]),
-                                     L.ptr(grads[i_g + 1]), M, D, 1, L.ptr(tgt), skip, L.ptr(dx_cur) if ln_oop else None, st),
-                "mt_layernorm_bwd")
-        return dx_new
+        L.check(lib.mt_layernorm_bwd(L.ptr(dxn_), L.ptr(r_["x"]), L.ptr(r_["stats"]), L.ptr(g_), L.ptr(dx_cur), L.ptr(grads[i_g]),
+                                     L.ptr(grads[i_g + 1]), M, D, 1, L.ptr(tgt), skip, None, st), "mt_layernorm_bwd")
+        return dx_cur
 
     # ---- head
     i0 = take(4)
@@ -150,9 +100,9 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
     # complete (tools/lab/queue_sync_cost.py), and a join stalls it until the side stream has caught up: 54 of them per step.
     # Now each sub-block writes du / dqkv / dx2 into FRESH buffers (the side launches that read the old ones pin them with
     # record_stream), so the main stream waits for nothing inside the layer loop.
-    join_each = os.environ.get("MT_TSF_JOIN", "0") == "1" and not defer
-    ln_oop = (defer or not join_each) and side.enabled
-    ln_split = ln_oop and not defer and os.environ.get("MT_LN_SPLIT", "1") != "0"     # dxn is then read on the side stream too: fresh per sub-block
+    # With the side stream off every side.launch runs inline and every side.wait returns at once.
+    join_each = os.environ.get("MT_TSF_JOIN", "0") == "1"
+    ln_oop = side.enabled and not join_each           # fresh du / dqkv / dxn / dx2 per sub-block (dxn is read on the side stream too)
 
     for li in reversed(range(model.depth)):
         rec = saved["layers"][li]
@@ -182,12 +132,10 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
             L.check(lib.mt_attn_bwd(L.ptr(r["qkv"]), L.ptr(do), L.ptr(dqkv), L.ptr(aux.mask), L.ptr(aux.ident), B, H, F, n, 2, scale, None, st),
                     "mt_attn_bwd")
             wgrad(dqkv, r["xn"], grads[i0 + 2], 3 * inner, D, M, 3 * inner, D, D)
-            e_dg = dgrad_skinny(dqkv, w_qkv, dxn, 3 * inner, wT[(li, 7)] if wT is not None else None)
+            dgrad(dqkv, w_qkv, 7, dxn, D, 3 * inner)
             dx_full = torch.zeros(B, N, D, dtype=torch.float32, device=dev)
             dx_full[:, 0, :] = dx2                                                          # the residual path: cls rows only
             dx2 = dx_full.view(M, D)
-            if e_dg is not None:
-                side.wait(e_dg)
             dx2 = ln_bwd(dxn, r, g, dx2, i0, grads[i0 - 1], 0)
             r.clear()
             # time attention: unchanged
@@ -195,21 +143,14 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
             g, b_, w_qkv, w_o, b_o = P[i0:i0 + 5]
             r = rec[0]
             side.wait()
-            if defer:
-                dqkv = torch.empty(M, 3 * inner, dtype=torch.float32, device=dev)
             e_dx = wgrad(dx2, r["o"], grads[i0 + 3], D, inner, M, D, inner, inner)
-            if wT is not None:
-                L.gemm(L.OP_NT, dx2, wT[(li, 3)], do, M, inner, D, D, D, inner)
-            else:
-                L.gemm(L.OP_NN, dx2, w_o, do, M, inner, D, D, inner, inner)
+            dgrad(dx2, w_o, 3, do, inner, D)
             L.check(lib.mt_attn_bwd(L.ptr(r["qkv"]), L.ptr(do), L.ptr(dqkv), L.ptr(aux.mask), L.ptr(aux.ident), B, H, F, n, 0, scale, None, st),
                     "mt_attn_bwd")
             wgrad(dqkv, r["xn"], grads[i0 + 2], 3 * inner, D, M, 3 * inner, D, D)
-            e_dg = dgrad_skinny(dqkv, w_qkv, dxn, 3 * inner, wT[(li, 2)] if wT is not None else None)
-            if e_dx is not None and not ln_oop:
+            dgrad(dqkv, w_qkv, 2, dxn, D, 3 * inner)
+            if join_each:
                 side.wait(e_dx)
-            if e_dg is not None:
-                side.wait(e_dg)
             tgt, skip = (grads[1], N) if li == 0 else (grads[i0 - 1], 0)
             dx2 = ln_bwd(dxn, r, g, dx2, i0, tgt, skip)
             r.clear()
@@ -218,11 +159,10 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
         i0 = take(6)
         g, b_, w1, b1, w2, b2 = P[i0:i0 + 6]
         r = rec[2]
-        if join_each or not ln_oop:
+        if join_each:
             side.wait()                               # du / dx2 readers of the previous sub-block are done
         if ln_oop:
             du = torch.empty(M, 8 * D, dtype=torch.float32, device=dev)       # the previous one may still be read by a weight gradient
-        if ln_split:
             dxn = torch.empty(M, D, dtype=torch.float32, device=dev)
         e_dx = wgrad(dx2, r["h"], grads[i0 + 4], D, 4 * D, M, D, 4 * D, 4 * D,
                      bias_out=grads[i0 + 5] if li == model.depth - 1 else None)
@@ -233,11 +173,9 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
             L.gemm(L.OP_NN, dx2, w2, du, M, 4 * D, D, D, 4 * D, 8 * D, epilogue=L.EPI_GEGLU_BWD, C2=r["u"], ldc2=8 * D, n_half=4 * D,
                    col_sum=grads[i0 + 3])             # net.0.bias gradient = column sums of du, taken in the epilogue
         wgrad(du, r["xn"], grads[i0 + 2], 8 * D, D, M, 8 * D, D, D)
-        e_dg = dgrad_skinny(du, w1, dxn, 8 * D, wT[(li, 12)] if wT is not None else None)
-        if e_dx is not None and not ln_oop:
+        dgrad(du, w1, 12, dxn, D, 8 * D)
+        if join_each:
             side.wait(e_dx)                           # LayerNorm backward updates dx2 in place
-        if e_dg is not None:
-            side.wait(e_dg)                           # ... and reads dxn, part of which the side stream summed
         dx2 = ln_bwd(dxn, r, g, dx2, i0, grads[i0 - 1], 0)                     # column sums -> space to_out.0.bias
         r.clear()
         # ---- attention blocks: x_out = o Wo^T + bo + x ; o = attn(qkv) ; qkv = LN(x) Wqkv^T
@@ -245,26 +183,19 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
             i0 = take(5)
             g, b_, w_qkv, w_o, b_o = P[i0:i0 + 5]
             r = rec[mode]
-            if join_each or not ln_oop:
+            if join_each:
                 side.wait()                           # dqkv / dx2 readers of the previous sub-block are done
             if ln_oop:
                 dqkv = torch.empty(M, 3 * inner, dtype=torch.float32, device=dev)    # (the old one is pinned by the launch reading it)
-            if ln_split:
                 dxn = torch.empty(M, D, dtype=torch.float32, device=dev)
-            dq = dqkv
             e_dx = wgrad(dx2, r["o"], grads[i0 + 3], D, inner, M, D, inner, inner)
-            if wT is not None:
-                L.gemm(L.OP_NT, dx2, wT[(li, 8 if mode == 1 else 3)], do, M, inner, D, D, D, inner)
-            else:
-                L.gemm(L.OP_NN, dx2, w_o, do, M, inner, D, D, inner, inner)
-            L.check(lib.mt_attn_bwd(L.ptr(r["qkv"]), L.ptr(do), L.ptr(dq), L.ptr(aux.mask), L.ptr(aux.ident), B, H, F, n, mode,
+            dgrad(dx2, w_o, 8 if mode == 1 else 3, do, inner, D)
+            L.check(lib.mt_attn_bwd(L.ptr(r["qkv"]), L.ptr(do), L.ptr(dqkv), L.ptr(aux.mask), L.ptr(aux.ident), B, H, F, n, mode,
                                     scale, None, st), "mt_attn_bwd")
-            wgrad(dq, r["xn"], grads[i0 + 2], 3 * inner, D, M, 3 * inner, D, D)
-            e_dg = dgrad_skinny(dq, w_qkv, dxn, 3 * inner, wT[(li, 7 if mode == 1 else 2)] if wT is not None else None)
-            if e_dx is not None and not ln_oop:
+            wgrad(dqkv, r["xn"], grads[i0 + 2], 3 * inner, D, M, 3 * inner, D, D)
+            dgrad(dqkv, w_qkv, 7 if mode == 1 else 2, dxn, D, 3 * inner)
+            if join_each:
                 side.wait(e_dx)
-            if e_dg is not None:
-                side.wait(e_dg)
             # the updated dx2 feeds the sub-block below: time attention's to_out.0.bias (index i0 - 1), the previous layer's
             # net.3.bias (i0 - 1 as well: parameter order is ..., w2, b2 | g, b, w_qkv, w_o, b_o | ...), or -- below layer 0 --
             # the patch embedding's bias (index 1), which does not see the cls rows
@@ -278,7 +209,7 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
     # ---- embeddings + patch embedding
     i0 = take(5)
     w_pe, b_pe, cls, pos_w, size_w = P[i0:i0 + 5]
-    dx = dx2.view(B, N, D)                            # (a fresh buffer per sub-block when the weight gradients are deferred)
+    dx = dx2.view(B, N, D)
     L.check(lib.mt_embed_bwd(L.ptr(dx), L.ptr(grads[i0 + 2]), L.ptr(grads[i0 + 3]), L.ptr(grads[i0 + 4]), L.ptr(aux.positions),
                              L.ptr(aux.sizes), B, F, n, D, pos_w.shape[0], size_w.shape[0] if size_w is not None else 0, st),
             "mt_embed_bwd")
@@ -292,25 +223,6 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
         L.gemm(L.OP_NN, dx2, w_pe, dfeat, Mt, C_in, D, D, C_in, C_in, a_map=tok_map)
     side.wait()
     assert idx == 0
-    if deferred:
-        late = L.SideStream(dev, name=":deferred-wgrad")
-        main = torch.cuda.current_stream(dev)
-        ready = torch.cuda.Event()
-        ready.record(main)                            # every operand of the recorded launches has been produced by now
-        late.stream.wait_event(ready)
-        with torch.cuda.stream(late.stream):
-            for run, reads in deferred:
-                for t in reads:
-                    t.record_stream(late.stream)      # freed by this function's return: the allocator must not hand them out early
-                run()
-        for g_ in grads:
-            if g_ is not None:
-                g_.record_stream(late.stream)
-                break                                 # (all views of one flat buffer)
-        done = torch.cuda.Event()
-        done.record(late.stream)
-        # end of the WHOLE backward pass (after the extractor's walk): the stream autograd ran on waits for the late launches
-        torch.autograd.Variable._execution_engine.queue_callback(lambda: torch.cuda.current_stream(dev).wait_event(done))
     L.grads_ready(model, params, flat_grads)
     out = []
     for gneed, gr in zip(need_dparams, grads):

@@ -5,7 +5,6 @@ HIP stream to the C ABI, and wires the result into autograd with ONE torch.autog
 transformer (inputs: token-major features + every parameter; the backward pass is our own reverse launch
 sequence, not torch autograd over torch ops).
 """
-import ctypes as C
 import os
 import types
 
@@ -117,8 +116,7 @@ def tsf_forward(model, feat, aux, params, B, F, n, save):
     _publish_index_flag(aux.err)
 
     saved = {"layers": []} if save else None
-    if save and M >= 4096 and L.gemm_split_enabled() and os.environ.get("MT_DGRAD_NT", "1") != "0" \
-            and not torch.cuda.is_current_stream_capturing():
+    if save and M >= 4096 and L.gemm_split_enabled() and not torch.cuda.is_current_stream_capturing():
         # Data gradients contract over a weight's ROW index: with the weight as stored that is a k-major B operand (eight strided
         # dword loads per thread in the split loop); over the transposed weight it is the same k-contiguous NT form as the forward
         # (two float4 loads): -10 % per launch (profiles/r02_gemm_split_lab.txt).  The 36 transposes (48 M floats) run on the
@@ -224,15 +222,8 @@ def tsf_forward(model, feat, aux, params, B, F, n, save):
             stats, u = None, None
         L.check(lib.mt_layernorm_fwd(L.ptr(x), L.ptr(g), L.ptr(b_), L.ptr(xn), L.ptr(stats), M, D, eps, None, st), "mt_layernorm_fwd")
         L.gemm(L.OP_NT, xn, w1, hbuf, M, 8 * D, D, D, D, 4 * D, epilogue=L.EPI_GEGLU, bias=b1, C2=u, ldc2=8 * D, n_half=4 * D)
-        # FF2 is skinny (N = 512 -> 396 output tiles on 256 CUs): 5 K-slices accumulated with fp32 atomics onto the residual
-        # even out the tail (measured 333 -> 270 us at B = 32).  Training only: atomics make the sum order -- the last bits of
-        # the logits -- vary from run to run, and inference (no saved buffers) stays bit-reproducible at every batch size.
-        if M >= 4096 and save and os.environ.get("MT_SKINNY_SPLIT") == "1":
-            x_new = x.clone() if save else x
-            L.gemm(L.OP_NT, hbuf, w2, x_new, M, D, 4 * D, 4 * D, 4 * D, D, epilogue=L.EPI_ATOMIC, bias=b2, split_k=5)
-        else:
-            x_new = _new(dev, B, N, D) if save else x
-            L.gemm(L.OP_NT, hbuf, w2, x_new, M, D, 4 * D, 4 * D, 4 * D, D, epilogue=L.EPI_BIAS_RES, bias=b2, R=x, ldr=D)
+        x_new = _new(dev, B, N, D) if save else x
+        L.gemm(L.OP_NT, hbuf, w2, x_new, M, D, 4 * D, 4 * D, 4 * D, D, epilogue=L.EPI_BIAS_RES, bias=b2, R=x, ldr=D)
         if save:
             rec[2] = dict(x=x, xn=xn, stats=stats, u=u, h=hbuf)
             saved["layers"].append(rec)
@@ -255,8 +246,7 @@ class _TSFFunction(torch.autograd.Function):
         B, F, n, grad_on = dims
         dims = (B, F, n)
         # needs_input_grad mirrors requires_grad even under torch.no_grad(), and grad mode is always off inside forward():
-        # the caller's grad mode comes in through `dims`.  Without it an eval forward would keep every activation and take
-        # the training-only split-K + atomics branch.
+        # the caller's grad mode comes in through `dims`.  Without it an eval forward would keep every activation.
         save = grad_on and any(ctx.needs_input_grad)
         ctx.model, ctx.dims, ctx.params = model, dims, params
         planes = tsf_planes.eligible(model, B * (1 + F * n), save)
@@ -273,7 +263,7 @@ class _TSFFunction(torch.autograd.Function):
                 logits, s_att, t_att, saved = tsf_planes.tsf_forward_planes(model, ins["feat"], a, params, B, F, n, save)
             elif tsf_planes.dropout_active(model):
                 raise NotImplementedError("attn-dropout / ff-dropout > 0 in train mode runs on the plane path only (MT_TSF_PLANES=1, "
-                                          "MT_GEMM_SPLIT=1, no MT_TSF_PRUNE_LAST / MT_WGRAD_DEFER, not under stream capture)")
+                                          "MT_GEMM_SPLIT=1, no MT_TSF_PRUNE_LAST, not under stream capture)")
             else:
                 logits, s_att, t_att, saved = tsf_forward(model, ins["feat"], a, params, B, F, n, save)
             if saved is not None:
@@ -304,23 +294,6 @@ class _TSFFunction(torch.autograd.Function):
         return (None, None, None) + plans.backward(ctx, "SizeInvariantTimeSformer", dlogits.contiguous(), body)
 
 
-_CHAIN_STREAMS = {}
-
-
-def _chain_stream(dev, i):
-    key = (str(dev), i)
-    if key not in _CHAIN_STREAMS:
-        _CHAIN_STREAMS[key] = torch.cuda.Stream(device=dev)
-    return _CHAIN_STREAMS[key]
-
-
-def _run_chain(model, x, mask, identities_mask, size_embedding, positions, grad_on):
-    b, f, c, h, w = x.shape
-    aux = _Aux(model, x, mask, identities_mask, size_embedding, positions)
-    feat = _as_tokens(x.float())
-    return _TSFFunction.apply(model, aux, (b, f, h * w, grad_on), feat, *model._param_list())
-
-
 def tsf_apply(model, x, mask, identities_mask, size_embedding, positions):
     if not x.is_cuda:
         raise L.MintimeHipError("SizeInvariantTimeSformer (MI355X build) needs device tensors; there is no CPU path")
@@ -332,42 +305,8 @@ def tsf_apply(model, x, mask, identities_mask, size_embedding, positions):
     if h * w != model.num_patches:
         raise ValueError(f"expected {model.num_patches} patches per slot, got {h * w}")
     grad_on = torch.is_grad_enabled()
-    chains = int(os.environ.get("MT_TSF_CHAINS", "1"))
-    # single-GPU experiment knob: a data-parallel reducer counts ONE grads_ready call per network and step (ddp.py), which the
-    # chains would fire once each -- with a reducer installed the clips stay in one chain
-    if chains > 1 and b >= 8 * chains and not torch.cuda.is_current_stream_capturing()             and getattr(model, "_grads_ready_hook", None) is None:
-        # Clips are independent inside the TimeSformer (no BatchNorm): run `chains` groups of clips as concurrent launch
-        # sequences on their own streams.  One sequence leaves the matrix cores idle during its LayerNorm / attention / epilogue
-        # phases and the tile tails; a second one fills them (measured in-step: two co-running kernels each stretch ~1.4x, not 2x).
-        main = torch.cuda.current_stream(x.device)
-        presplit = tsf_planes.eligible(model, (b // chains) * (1 + f * h * w), grad_on)
-        if presplit:
-            # the chains share the weights' operand planes: write them ONCE on the main stream, before the fork (each chain re-writing
-            # them while another chain's GEMMs read them was an unsynchronised -- if value-preserving -- write)
-            tsf_planes.weight_planes(model, model._param_list(), grad_on)
-            model.__dict__["_wplanes_presplit"] = True
-        ready = torch.cuda.Event()
-        ready.record(main)
-        outs = []
-        try:
-            for ci in range(chains):
-                lo, hi = ci * b // chains, (ci + 1) * b // chains
-                st = _chain_stream(x.device, ci)
-                st.wait_event(ready)
-                x.record_stream(st)
-                with torch.cuda.stream(st):
-                    sl = lambda t: None if t is None else t[lo:hi]
-                    outs.append(_run_chain(model, x[lo:hi], sl(mask), sl(identities_mask), sl(size_embedding), sl(positions), grad_on))
-        finally:
-            model.__dict__.pop("_wplanes_presplit", None)
-        for ci in range(chains):
-            main.wait_stream(_chain_stream(x.device, ci))
-        for o in outs:
-            for t in o:
-                t.record_stream(main)
-        outs = tuple(torch.cat([o[k] for o in outs], dim=0) for k in range(len(outs[0])))
-    else:
-        outs = _run_chain(model, x, mask, identities_mask, size_embedding, positions, grad_on)
+    aux = _Aux(model, x, mask, identities_mask, size_embedding, positions)
+    outs = _TSFFunction.apply(model, aux, (b, f, h * w, grad_on), _as_tokens(x.float()), *model._param_list())
     if model.require_attention:
         return outs[0], [outs[1], outs[2]]       # order [space, time] (reference :271)
     return outs[0]

@@ -24,17 +24,13 @@ from . import lib as L
 from . import plans
 from .lib import _new
 
-# LayerNorm backward: parameter-gradient column sums folded into the rows kernel as per-block partials (MT_LN_FOLD=0: the second pass
-# over dy / x / dx on the weight-gradient stream)
-LN_FOLD = os.environ.get("MT_LN_FOLD", "1") != "0"
-
 _SEL = (2, 3, 7, 8, 12, 14)      # offsets of w_qkv, w_o (time); w_qkv, w_o (space); net.0 / net.3 weights inside a layer's 16 parameters
 
 
 def eligible(model, M, save):
     if os.environ.get("MT_TSF_PLANES", "1") == "0" or not L.gemm_split_enabled():
         return False
-    if os.environ.get("MT_TSF_PRUNE_LAST", "0") != "0" or os.environ.get("MT_WGRAD_DEFER", "0") != "0":
+    if os.environ.get("MT_TSF_PRUNE_LAST", "0") != "0":
         return False
     if torch.cuda.is_current_stream_capturing() and save:
         return False
@@ -80,9 +76,8 @@ def weight_planes(model, params, training):
     # The planes are re-written on EVERY forward (one launch, ~60 us for the 54 matrices): updates that move no version counter
     # (p.data.copy_, dist.broadcast(p.data), a fused optimizer step through raw pointers) cannot leave them stale, and a forward
     # captured into a HIP graph (harness.GraphedEval) holds the split as a node, so its replays read the weights of the replay's time.
-    if not model.__dict__.get("_wplanes_presplit"):  # MT_TSF_CHAINS: tsf_apply split once, before the chains' streams forked
-        L.check(lib.mt_split_planes_blk_multi(L.ptr(cache["table"]), cache["count"], cache["blocks"], L.stream_ptr()),
-                "mt_split_planes_blk_multi")         # (L.ptr: a launch plan being recorded pins the table)
+    L.check(lib.mt_split_planes_blk_multi(L.ptr(cache["table"]), cache["count"], cache["blocks"], L.stream_ptr()),
+            "mt_split_planes_blk_multi")             # (L.ptr: a launch plan being recorded pins the table)
     return cache["holder"], cache["serial"].touch(ws)
 
 
@@ -228,7 +223,7 @@ def tsf_backward_planes(model, feat, aux, params, dims, saved, dlogits, need_dfe
         dx_new = torch.empty_like(dx_cur)
         dx_p = L.planes_empty(M, D, dev)
         x_, st_ = r_["x"], r_["stats"]
-        if LN_FOLD and D <= 512:
+        if D <= 512:
             # the rows kernel also leaves per-block partial column sums; the weight-gradient stream only adds 6 MB of them up
             nb = lib.mt_layernorm_bwd_rows_blocks(M)
             part = _new(dev, nb, 3, D)
@@ -238,6 +233,7 @@ def tsf_backward_planes(model, feat, aux, params, dims, saved, dlogits, need_dfe
                                                                          L.ptr(tgt), L.stream_ptr()), "mt_layernorm_bwd_cols_reduce"),
                         reads=(part,))
             return dx_new, dx_p
+        # wider rows: the column sums are a second pass over dy / x / dx on the weight-gradient stream
         L.check(lib.mt_layernorm_bwd_rows(L.ptr(dxn_), L.ptr(x_), L.ptr(st_), L.ptr(g_), L.ptr(dx_new), L.ptr(dx_cur), M, D,
                                           L.ptr(dx_p), st), "mt_layernorm_bwd_rows")
         side.launch(lambda: L.check(lib.mt_layernorm_bwd_cols(L.ptr(dxn_), L.ptr(x_), L.ptr(st_), L.ptr(dx_new), L.ptr(grads[i_g]),

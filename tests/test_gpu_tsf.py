@@ -1,4 +1,5 @@
 """GPU parity of the HIP SizeInvariantTimeSformer against the CPU oracle and the reference-generated fixtures."""
+import functools
 import os
 
 import pytest
@@ -181,7 +182,8 @@ def test_clip_with_a_fully_padded_identity_and_a_single_valid_slot():
 
 def test_full_size_batch_logits_and_all_gradients_vs_oracle():
     """The configuration bench.py times (config 3: B = 32, 8 slots, 2 identities, M = 12 576 token rows): at this size the engine
-    takes its large-M branches (FF2 and the N = 512 data gradients as split-K + atomics, 64x64 tiles, L2-blocked tile order).
+    takes its large-M branches (every Linear layer and its two gradients on plane operands, weight gradients as split-K + fp32
+    atomics on the side stream, L2-blocked tile order).
     Logits, both cls attentions and EVERY parameter gradient against the CPU oracle (size_invariant_timesformer.py:263-268)."""
     B, Fr, C, seed = 32, 8, 1280, 7
     cfg = arch.default_tsf_config(C, Fr)
@@ -209,6 +211,56 @@ def test_full_size_batch_logits_and_all_gradients_vs_oracle():
             assert float(p.grad.abs().max()) == 0.0, k
         else:
             assert_close(p.grad, ref, REL_TOL, "grad " + k)
+
+
+@functools.lru_cache(maxsize=None)
+def _large_m_case():
+    """Inputs and the oracle's results (computed once, read-only) of test_in_kernel_split_engine_at_large_m_vs_oracle."""
+    B, Fr, C, seed = 32, 8, 1280, 13
+    cfg = arch.default_tsf_config(C, Fr, num_patches=16)
+    cfg["model"]["depth"] = 2
+    sd = synth.tsf_state(cfg, seed)
+    feats = synth.features(B, Fr, C, seed, hw=4)
+    aux = synth.clip_inputs(B, Fr, 2, seed, ragged=True, num_patches=16, with_video=False)
+    w = torch.linspace(-1.0, 1.3, B).reshape(B, 1)          # (weights that do not sum to zero: d/d(head bias) = sum(w))
+    osd = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    xo = feats.clone().requires_grad_(True)
+    oout, (o_s, o_t) = O.tsf_forward(osd, cfg, xo, aux["mask"], aux["identities_mask"], aux["size_embedding"], aux["positions"],
+                                     require_attention=True)
+    (oout * w).sum().backward()
+    ref = dict(logits=oout.detach(), space=o_s.detach(), time=o_t.detach(), dfeat=xo.grad, grads={k: v.grad for k, v in osd.items()})
+    return cfg, seed, feats, aux, w, ref
+
+
+@pytest.mark.parametrize("env", [{}, {"MT_TSF_JOIN": "1"}, {"MT_TSF_PRUNE_LAST": "1"}], ids=["default", "join", "prune_last"])
+def test_in_kernel_split_engine_at_large_m_vs_oracle(env, monkeypatch):
+    """MT_TSF_PLANES=0 in training at M >= 4096 (tsf_engine.tsf_forward / tsf_backward.tsf_backward): the size at which the data
+    gradients switch to the NT form over the transposed-weight cache, the LayerNorm backward goes out of place (rows on the main
+    stream, column sums on the weight-gradient stream) and the weight gradients run on the side stream -- alone, with the
+    per-sub-block joins of MT_TSF_JOIN=1, and with the last layer's dead rows pruned.  Smallest shape that takes every one of those
+    branches: 16 patches per slot, depth 2, B = 32 -> N = 129, M = 4128.  Same kernels and width as the full-size test above, hence
+    its gate."""
+    monkeypatch.setenv("MT_TSF_PLANES", "0")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    cfg, seed, feats, aux, w, ref = _large_m_case()
+    model, _ = _build(cfg, seed, require_attention=True)
+    x = feats.cuda().requires_grad_(True)
+    out, (s_att, t_att) = model(x, mask=aux["mask"].cuda(), identities_mask=aux["identities_mask"].cuda(),
+                                size_embedding=aux["size_embedding"], positions=aux["positions"].cuda())
+    assert x.shape[0] * (1 + x.shape[1] * x.shape[3] * x.shape[4]) == 4128
+    assert getattr(model, "_wT_cache", {}).get("serial", 0) >= 1, "the transposed-weight (large-M) branch was not taken"
+    (out.cpu() * w).sum().backward()
+    assert_close(out, ref["logits"], REL_TOL, "logits")
+    assert_close(s_att, ref["space"], REL_TOL, "space cls attention")
+    assert_close(t_att, ref["time"], REL_TOL, "time cls attention")
+    assert_close(x.grad, ref["dfeat"], REL_TOL, "feature gradient")
+    for k, p in model.named_parameters():
+        g = ref["grads"][k]
+        if float(g.abs().max()) == 0.0:
+            assert float(p.grad.abs().max()) == 0.0, k
+        else:
+            assert_close(p.grad, g, REL_TOL, "grad " + k)
 
 
 def test_out_of_range_indices_are_caught_not_dereferenced():
