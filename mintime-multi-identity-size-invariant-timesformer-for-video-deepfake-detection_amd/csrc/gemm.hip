@@ -159,17 +159,15 @@ static int gemm_impl(const mt_gemm_desc* d, void* stream) {
     if (rc <= 0) return rc;
   }
   int cfg = pick_cfg(d->op, d->M, d->N, d->prologue, d->epilogue);
-  static const int wg64_var = env_int("MT_CONV_WG64", 2);      // lab: 0 = the 128 x 64 tile, 1 = six wavefronts
-  if (d->op == MT_OP_TN && d->b_prologue == MT_BPRO_IM2COL && d->epilogue == MT_EPI_ATOMIC && d->M <= 64 && d->N > 192 && d->N <= 288 && wg64_var != 0)
-    cfg = (det_enabled() || wg64_var == 1) ? CFG_WG64 : CFG_WG64K;   // (deterministic mode writes per-split slabs: one writer per tile)
+  if (d->op == MT_OP_TN && d->b_prologue == MT_BPRO_IM2COL && d->epilogue == MT_EPI_ATOMIC && d->M <= 64 && d->N > 192 && d->N <= 288)
+    cfg = det_enabled() ? CFG_WG64 : CFG_WG64K;   // (deterministic mode writes per-split slabs: one writer per tile)
   const TileGrid tg = tile_grid(d->M, d->N, kCfg[cfg].bm, kCfg[cfg].bn, (int64_t)kCfg[cfg].bn * d->K * 4);
   dim3 grid(tg.grid_x, 1, 1);
   a.group_n = tg.group_n;
   a.trace = g_trace;
 
   // im2col prologues: the granule form (gemm_core.hpp) for float images with C % 4 == 0 and k <= 5, else the per-element gather
-  static const bool im_any = env_set("MT_IM2COL_ANY");                  // lab: the per-element gather everywhere
-  const bool im_granule = (d->conv_C & 3) == 0 && !d->conv_src_u8 && d->conv_k * d->conv_k <= 32 && !im_any;
+  const bool im_granule = (d->conv_C & 3) == 0 && !d->conv_src_u8 && d->conv_k * d->conv_k <= 32;
 #define COMBO(OP, AL, BL, PRO, EPI)                                                        \
   if (d->op == OP && d->prologue == PRO && d->epilogue == EPI)                             \
     return launch<AL, BL, PRO, EPI>(cfg, a, grid, s);

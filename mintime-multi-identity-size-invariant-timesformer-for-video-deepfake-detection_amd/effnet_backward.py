@@ -12,20 +12,6 @@ from .lib import _new
 # slower than the two kernels on two streams; with the branch-free tap reads of round 6 it wins for the 3x3 layers (one box, serialised
 # extractor 21.82 -> 21.35 ms, step 44.99 -> 44.43 ms; all layers: 21.34 / 44.60): "3" = the 3x3 layers (default), "1" = every layer, "0" = off.
 FUSED_DW = __import__("os").environ.get("MT_DW_FUSED", "3")
-# Squeeze-excite stage of the reverse walk without the project conv's data gradient `da` in memory: the GEMM  dz_p . W_project  is
-# run twice and consumed in its accumulators (MT_EPI_SE_RED: d gate; MT_EPI_ACT_BWD: du of the depthwise BatchNorm + its sums).
-# 3 passes over a block's expanded tensor (read z_d, read z_d, write du_d) instead of 6 (write da | read da, z_d | read da, z_d,
-# write du_d), two launches fewer -- and SLOWER on every block (profiles/r03_se_fused_epilogue_vs_streaming.txt: block 1
-# 406 -> 744 us, the 7x7 blocks 126 -> 193 us, step +1.3 ms): a one-tile-per-block GEMM with a load-z / swish / store epilogue
-# per lane-column runs at 1.3-3.2 TB/s where the float4 streaming kernels it replaces run at 4.5-5.5.  Opt-in (MT_SE_FUSED=1; no test
-# runs the engine with it); the two epilogues themselves are parity-tested per kernel against fp64 on the register-staged and the
-# LDS-DMA kernels (tests/test_gpu_gemm_ops.py).
-SE_FUSED = __import__("os").environ.get("MT_SE_FUSED", "0") != "0"
-EXPAND_FUSED = __import__("os").environ.get("MT_EXPAND_FUSED", "1") != "0"
-WIDE_WGRAD = __import__("os").environ.get("MT_WIDE_WGRAD", "1") != "0"      # late-stage project-conv weight gradients: wide_wgrad.hip
-# squeeze-excite reverse stage of the early blocks (stages 0-2) as two STREAMING passes that rebuild the project conv's data gradient
-# from the narrow gradient (skinny_se.hip): 3 instead of 6 passes over the expanded tensor, no da tensor
-SE_STREAM = __import__("os").environ.get("MT_SE_STREAM", "1") != "0"     # expand-conv data + weight gradient in one pass (stages 1-3)
 
 
 def _splits(rows):
@@ -90,8 +76,6 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
     det = L.deterministic()
     pool = _StatsPool(dev, total_c, det)
     slots = -SLOTS if det else SLOTS       # deterministic mode: BatchNorm-backward sums as integer limbs (csrc/common.hpp stat_add)
-    expand_fused, wide_wgrad, se_stream, se_fused = (EXPAND_FUSED and not det, WIDE_WGRAD and not det, SE_STREAM and not det,
-                                                     SE_FUSED and not det)
     fused_dw = "0" if det else FUSED_DW
 
     def bn_finalize(bnctx, sums, gidx_gamma, d=None, z=None, rows=0):
@@ -107,13 +91,12 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
                 "mt_bn_act_bwd")
         return sums
 
-    def conv1x1_bwd(du, z, kabc, w, x_in, rows, cout, cin, gw_idx, need_dx_in, res=None, b_pro=None, epi=None, pl=None):
+    def conv1x1_bwd(du, z, kabc, w, x_in, rows, cout, cin, gw_idx, need_dx_in, res=None, b_pro=None, pl=None):
         """z = x_in . w^T with dz = ka*du+kb*z+kc.  Returns dx_in [rows, cin] (+res) or None.
-        epi = (kind, out, kwargs): the data gradient is not stored but consumed by mt_gemm's SE_RED / ACT_BWD epilogue.
         pl = {"w_p": weight planes, "x_p": planes of the forward operand or None}: the late stages' plane path -- dz is evaluated ONCE,
         as planes (mt_bn_bwd_apply_planes), and feeds the data-gradient GEMM (weight planes read along their rows) and, when the
         forward kept its operand as planes, the weight-gradient GEMM."""
-        if pl is not None and epi is None:
+        if pl is not None:
             dz_p = L.planes_empty(rows, cout, dev)
             L.check(lib.mt_bn_bwd_apply_planes(L.ptr(du), L.ptr(z), L.ptr(kabc), L.ptr(dz_p), rows, cout, st), "mt_bn_bwd_apply_planes")
             wdone = False
@@ -138,7 +121,7 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
         if b_pro is not None:
             kw = dict(b_prologue=L.BPRO_BN_SWISH_GATE, b_scale=b_pro[0], b_shift=b_pro[1], b_gate=b_pro[2], b_hw=b_pro[3])
         reads = (du, z, x_in, kabc) + (tuple(b_pro[:3]) if b_pro is not None else ())
-        if (expand_fused and b_pro is None and epi is None and need[gw_idx] and need_dx_in and rows >= 100000
+        if (not det and b_pro is None and need[gw_idx] and need_dx_in and rows >= STREAM_ROWS
                 and lib.mt_conv1x1_bwd_fused_supported(cout, cin)):
             # expand convs of stages 1-3: data AND weight gradient in one streaming pass over du (z is folded: 1 instead of 4 passes
             # over the widest tensors of the step; skinny_bwd.hip).  Runs on the main stream: it is the data gradient's critical path.
@@ -149,14 +132,14 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
             return dx_in
         if not need[gw_idx]:
             pass                                      # frozen weight: no launch
-        elif rows >= 100000 and not det and lib.mt_conv1x1_wgrad_supported(cout, cin):
+        elif rows >= STREAM_ROWS and not det and lib.mt_conv1x1_wgrad_supported(cout, cin):
             run["wgrad_launches"] += 1
             # few channels, very many rows: the result stays in MFMA accumulators while the rows stream (skinny_wgrad.hip)
             bp = b_pro if b_pro is not None else (None, None, None, 1)
             side.launch(lambda: L.check(lib.mt_conv1x1_wgrad(L.ptr(du), L.ptr(z), L.ptr(kabc), L.ptr(x_in), L.ptr(bp[0]), L.ptr(bp[1]),
                                                              L.ptr(bp[2]), bp[3], L.ptr(grads[gw_idx]), rows, cout, cin,
                                                              L.stream_ptr()), "mt_conv1x1_wgrad"), reads=reads)
-        elif wide_wgrad and b_pro is not None and lib.mt_conv1x1_wgrad_wide_supported(cout, cin):
+        elif not det and b_pro is not None and lib.mt_conv1x1_wgrad_wide_supported(cout, cin):
             run["wgrad_launches"] += 1
             # project convs of the late stages: 128-column slabs of the result, both operand transforms applied once (wide_wgrad.hip)
             side.launch(lambda: L.check(lib.mt_conv1x1_wgrad_wide(L.ptr(du), L.ptr(z), L.ptr(kabc), L.ptr(x_in), L.ptr(b_pro[0]),
@@ -169,11 +152,6 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
                         reads=reads)
         if not need_dx_in:
             return keep_dx
-        if epi is not None:
-            for kind, out, kw2 in epi:
-                L.gemm(L.OP_NN, du, w, out, rows, cin, cout, cout, cin, cin, prologue=L.PRO_BN_BWD, epilogue=kind, A2=z,
-                       scale=kabc[0], shift=kabc[1], gate=kabc[2], **kw2)
-            return None
         dx_in = _new(dev, rows, cin)
         if rows >= STREAM_ROWS and lib.mt_conv1x1_rows_supported(cout, cin, 2):
             # data gradient as a streaming kernel: a = dz (BatchNorm backward folded on load), W used transposed
@@ -226,8 +204,11 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
                                   L.ptr(_rec["hidden"]), L.ptr(_rec["pooled"]), L.ptr(P[_se]), L.ptr(P[_se + 2]), L.ptr(_dg), L.ptr(_dp),
                                   L.ptr(_dh), L.ptr(_dpo), L.ptr(grads[_se]), L.ptr(grads[_se + 1]), L.ptr(grads[_se + 2]),
                                   L.ptr(grads[_se + 3]), N, _hw, _s.cexp, _s.cse, parts, L.ptr(_scr), L.stream_ptr()), "mt_se_bwd")
-        if (se_stream and not se_fused and M_out >= 100000
-                and lib.mt_se_stage_fused_supported(s.cout, s.cexp, hw)):
+        # early blocks (stages 0-2): two STREAMING passes that rebuild the project conv's data gradient from the narrow gradient
+        # (skinny_se.hip): 3 instead of 6 passes over the expanded tensor, no da tensor.  (The same stage as mt_gemm epilogues measured
+        # slower, profiles/r03_se_fused_epilogue_vs_streaming.txt; MT_EPI_SE_RED / MT_EPI_ACT_BWD remain mt_gemm epilogues, parity-tested
+        # per kernel in tests/test_gpu_gemm_ops.py.)
+        if not det and M_out >= STREAM_ROWS and lib.mt_se_stage_fused_supported(s.cout, s.cexp, hw):
             conv1x1_bwd(dsrc, rec["z_p"], kabc_p, P[ix["p"]], rec["z_d"], M_out, s.cout, s.cexp, ix["p"], False, b_pro=b_pro)   # weight gradient only
             def stage(mode, dg, g_, dpo, mi, out, st_):
                 L.check(lib.mt_se_stage_fused(L.ptr(dsrc), L.ptr(rec["z_p"]), L.ptr(kabc_p), L.ptr(P[ix["p"]]), L.ptr(rec["z_d"]),
@@ -242,23 +223,6 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
             da = _new(dev, M_out, s.cexp)                                         # (c+e) du_d and the bn1 sums
             sums = pool.take(s.cexp)
             stage(1, None, rec["gate"], dpooled, bn_d.mean_invstd, da, sums)
-        elif se_fused:
-            # (c+d) d gate straight from the accumulators of  dz_p . Wp  (da is never written)
-            L.zero_(dgate)
-            conv1x1_bwd(dsrc, rec["z_p"], kabc_p, P[ix["p"]], rec["z_d"], M_out, s.cout, s.cexp, ix["p"], True, b_pro=b_pro,
-                        epi=[(L.EPI_SE_RED, dgate, dict(C2=rec["z_d"], ldc2=s.cexp, epi=(bn_d.scale, bn_d.shift, None, None, None, hw)))])
-            se_part(4)                                # dgate -> dpooled
-            if any(need[se:se + 4]):
-                run["wgrad_launches"] += 1
-                side.launch(lambda: se_part(2), reads=(dpre2, dhid, rec["hidden"], rec["pooled"]))
-            # (c+e) the same product again, through gate / pooled gradient / swish' / bn1 sums: du_d
-            da = _new(dev, M_out, s.cexp)
-            sums = pool.take(s.cexp)
-            need_save, need[ix["p"]] = need[ix["p"]], False        # the weight gradient was launched by the first call
-            conv1x1_bwd(dsrc, rec["z_p"], kabc_p, P[ix["p"]], rec["z_d"], M_out, s.cout, s.cexp, ix["p"], True, b_pro=b_pro,
-                        epi=[(L.EPI_ACT_BWD, da, dict(C2=rec["z_d"], ldc2=s.cexp, stats=sums, stats_slots=slots,
-                                                      epi=(bn_d.scale, bn_d.shift, rec["gate"], dpooled, bn_d.mean_invstd, hw)))])
-            need[ix["p"]] = need_save
         else:
             da = conv1x1_bwd(dsrc, rec["z_p"], kabc_p, P[ix["p"]], rec["z_d"], M_out, s.cout, s.cexp, ix["p"], True, b_pro=b_pro,
                              pl=dict(w_p=rec["wp_p"], x_p=rec["a_p"]) if rec.get("wp_p") is not None else None)
@@ -313,7 +277,7 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
             # (h,i,j) bn0 + expand conv: z_e = y_in . We^T
             kabc_e = bn_finalize(in_bn, sums_in, ix["e"] + 1, du_in, rec["dw_in"], M_in)
             z_e = rec["z_e"]
-            if z_e is None and not (expand_fused and need[ix["e"]] and need_below[bi] and M_in >= 100000
+            if z_e is None and not (not det and need[ix["e"]] and need_below[bi] and M_in >= STREAM_ROWS
                                     and lib.mt_conv1x1_bwd_fused_supported(s.cexp, s.cin)):
                 # recompute form, but this pass takes a branch that reads the expanded pre-activation (a frozen neighbour): rebuild it
                 z_e = _new(dev, M_in, s.cexp)

@@ -10,11 +10,11 @@ from . import plans
 from .lib import _new
 
 SLOTS = 32   # replicated fp64 BatchNorm accumulators (spreads atomic traffic)
-STEM_DIRECT = __import__("os").environ.get("MT_STEM_DIRECT", "1") != "0"    # 0 = the im2col-prologue GEMM
-STREAM_ROWS = int(__import__("os").environ.get("MT_STREAM_ROWS", "100000"))   # 1x1 convs with at least this many rows use the streaming kernels
+STREAM_ROWS = 100000   # 1x1 convs with at least this many rows use the streaming kernels (forward and backward)
 # Late stages (14 x 14 and 7 x 7 grids, the head) on plane operands (csrc/effnet_planes.hip, gemm_planes.hpp): expand convolutions
 # whose input grid is at most EF_PLANES_EXPAND_HW wide, project convolutions whose output grid is at most EF_PLANES_PROJECT_HW wide
-# (tools/lab/ef_planes_lab.py: at 14 x 14 the project convolution's producer pass costs what its GEMM saves).  MT_EF_PLANES=0: off.
+# (tools/lab/ef_planes_lab.py: at 14 x 14 the project convolution's producer pass costs what its GEMM saves).
+EF_PLANES_EXPAND_HW, EF_PLANES_PROJECT_HW = 14, 7
 # Early stages (blocks 1-3: 112^2 / 56^2 grids): expand convolution recomputed inside the depthwise kernels from the 16- / 24-channel
 # block input (csrc/rc.hpp) -- the 6x wider expanded tensor is never written (forward) nor read (depthwise forward, data and weight
 # gradient); in train mode its BatchNorm statistics come from a statistics-only pass over the block input.  Measured (round 6,
@@ -23,9 +23,6 @@ STREAM_ROWS = int(__import__("os").environ.get("MT_STREAM_ROWS", "100000"))   # 
 # the recompute removes, and it adds MFMA + staging work to them.  OFF by default; MT_EF_RC=1 switches it on (parity-tested).
 EF_RC = __import__("os").environ.get("MT_EF_RC", "0") != "0"
 EF_RC_MIN_ROWS = int(__import__("os").environ.get("MT_EF_RC_ROWS", "100000"))    # pixel rows from which the recompute form is used
-EF_PLANES = __import__("os").environ.get("MT_EF_PLANES", "1") != "0"
-EF_PLANES_EXPAND_HW = int(__import__("os").environ.get("MT_EF_PLANES_EXPAND_HW", "14"))
-EF_PLANES_PROJECT_HW = int(__import__("os").environ.get("MT_EF_PLANES_PROJECT_HW", "7"))
 
 
 def param_list(model):
@@ -91,7 +88,7 @@ def _track(counter):
 
 def planes_scope(model, N):
     """(expand-on-planes?, project-on-planes?) per block + head, for a batch of N crops: the plane GEMM wants >= 512 pixel rows."""
-    on = EF_PLANES and L.gemm_split_enabled()
+    on = L.gemm_split_enabled()
     blocks = model._blocks
     exp = [on and b.spec.has_expand and b.spec.hin <= EF_PLANES_EXPAND_HW and N * b.spec.hin * b.spec.hin >= 512 and b.spec.cin % 4 == 0
            for b in blocks]
@@ -204,7 +201,7 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
     z = _new(dev, N * Hc * Wc, arch.STEM_COUT)
     # stem: streaming MFMA kernel (stem_fwd.hip; uint8 crops converted on the fly, BatchNorm statistics in the same pass).  The
     # im2col-prologue GEMM it replaced (K = 27 taps padded to 28) stays the path for crops wider than the kernel's LDS row tile.
-    if W <= 512 and H == W and STEM_DIRECT:
+    if W <= 512 and H == W:
         L.check(lib.mt_stem_conv_fwd(L.ptr(x_nhwc), 1 if x_nhwc.dtype == torch.uint8 else 0, L.ptr(w_stem), L.ptr(z),
                                      sptr(bn), slots, N, H, W, st), "mt_stem_conv_fwd")
     else:

@@ -15,12 +15,12 @@ from .lib import _new
 RELU, NONE = 2, 0
 
 
-# pointwise convolutions with at least this many input channels run on plane operands (MT_XC_PLANES=0: the in-kernel-split loop)
-XC_PLANES = __import__("os").environ.get("MT_XC_PLANES", "1") != "0"
-PLANES_MIN_C = int(__import__("os").environ.get("MT_XC_PLANES_MIN_C", "256"))   # (128: +0.4 ms in config 5 once the 4 GB operand limit is respected, lib.planes_fit)
+# pointwise convolutions with at least this many input channels run on plane operands (MT_GEMM_SPLIT=0: none does, all take mt_gemm)
+PLANES_MIN_C = 256   # (128: +0.4 ms in config 5 once the 4 GB operand limit is respected, lib.planes_fit)
 DW_PLANES = __import__("os").environ.get("MT_XC_DW_PLANES", "1") != "0"   # 0: depthwise output as fp32 + mt_split_planes_blk (round 4)
-CONV2_WGRAD_SIDE = float(__import__("os").environ.get("MT_XC_CONV2_WGRAD_SIDE", "0.7"))   # share of conv2's weight gradient on the side stream
-XC_STEM = __import__("os").environ.get("MT_XC_STEM", "1") != "0"             # 0: conv1 as an im2col GEMM (round 4)
+# share (of the images) of conv2's weight gradient on the side stream (round 5: 1.0: 203.0 ms, 0.7: 201.7 on one box; round 6 with the
+# one-tile weight gradient: 0.5 / 0.7 / 1.0 within 0.6 ms)
+CONV2_WGRAD_SIDE = 0.7
 SKIP_HALF = __import__("os").environ.get("MT_XC_SKIP_HALF", "1") != "0"    # 0: the skip path's data gradient scattered into a zeroed full-size tensor
 POOL_ARG = __import__("os").environ.get("MT_XC_POOL_ARG", "1") != "0"      # 0: the adjoint of the max-pool as an arg-max scatter (round 4)
 
@@ -124,7 +124,7 @@ def xception_forward(model, x, params, training, save, plan=None):
     consts = _Consts(dev)
     slots = -SLOTS if det else SLOTS          # deterministic mode: BatchNorm sums as integer limbs -- order-independent, no second pass
     epi = L.EPI_STATS if training else L.EPI_STORE
-    planes_on = XC_PLANES and L.gemm_split_enabled()
+    planes_on = L.gemm_split_enabled()
     wplanes = model.__dict__.setdefault("_xc_wplanes", _WeightPlanes())
     if planes_on:
         wplanes.begin(lib)
@@ -184,7 +184,7 @@ def xception_forward(model, x, params, training, save, plan=None):
     # ---- conv1 (3x3 s2 p0, 3 -> 32) and conv2 (3x3 s1 p0, 32 -> 64) as im2col GEMMs
     w1, g1, b1, w2, g2, b2 = next(it), next(it), next(it), next(it), next(it), next(it)
     H1 = (H - 3) // 2 + 1
-    if XC_STEM and W <= 512:
+    if W <= 512:
         # conv1 = the EfficientNet stem's streaming MFMA kernel without padding (K = 27 is far too short for the im2col GEMM: 4.3 ms
         # against 0.5 at 512 crops); reads uint8 crops as well
         bn1 = _BNCtx(dev, 32, training, pool)
@@ -357,8 +357,10 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
             L.check(fn(L.ptr(dd), L.ptr(dd), L.ptr(kid), L.ptr(w_dw), L.ptr(src.t), L.ptr(rec["sc"]), L.ptr(rec["sh"]),
                        L.ptr(src.bn.mean_invstd) if has_bn else None, L.ptr(du_in), L.ptr(sums_in), slots, L.ptr(grads[pi]), N, Hh, Hh, ci,
                        3, 1, parts, rec["eff"], L.ptr(res_pre), L.ptr(res_post), L.stream_ptr()), "mt_dwconv_bwd")
-        if XC_DW_FUSED and not det:
-            dw_part(3)            # data + weight gradient from one pass (effnet_backward.FUSED_DW; deterministic mode keeps the logged weight-gradient kernel)
+        if not det:
+            # data + weight gradient from one pass (effnet_backward.FUSED_DW; all of Xception's depthwise layers are 3x3 stride 1):
+            # config 5 200.0 -> 193.5 ms.  Deterministic mode keeps the two kernels on two streams (the logged weight-gradient kernel)
+            dw_part(3)
         else:
             side.launch(lambda: dw_part(1), reads=(dd, kid, src.t, rec["sc"], rec["sh"]))
             dw_part(2)
@@ -457,14 +459,13 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
     k1 = bn_kabc(bn1, bn_sums(da1, z1, bn1, M1, act=RELU, dout=du1), 1, du1, z1, M1)
     dx = None
     if need_dx:
-        if not (XC_STEM and W <= 512):
-            raise NotImplementedError("gradient w.r.t. the input crops: mt_stem_conv_dgrad_valid takes crops of at most 512 columns "
-                                      "and needs MT_XC_STEM=1")
+        if W > 512:
+            raise NotImplementedError("gradient w.r.t. the input crops: mt_stem_conv_dgrad_valid takes crops of at most 512 columns")
         # the last operator of the walk: the transposed conv1, 32 -> 3 channels (csrc/stem_dgrad.hip)
         dx = _new(dev, N, H, W, 3)
         L.check(lib.mt_stem_conv_dgrad_valid(L.ptr(du1), L.ptr(z1), L.ptr(k1), L.ptr(P[0]), L.ptr(dx), N, H, W, L.stream_ptr()),
                 "mt_stem_conv_dgrad_valid")
-    if XC_STEM and W <= 512:
+    if W <= 512:
         L.check(lib.mt_stem_conv_wgrad_valid(L.ptr(du1), L.ptr(z1), L.ptr(k1), L.ptr(saved["x"]), 1 if saved["x"].dtype == torch.uint8 else 0,
                                              L.ptr(grads[0]), N, H, W, L.stream_ptr()), "mt_stem_conv_wgrad_valid")
     else:
@@ -485,11 +486,7 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
 
 def _plannable():
     """The recorded form covers the default kernels only: the lab alternatives issue torch fills / scatters a recording cannot see."""
-    return SKIP_HALF and POOL_ARG and XC_STEM and XC_PLANES and DW_PLANES and XC_PLAN
-
-
-XC_DW_FUSED = __import__("os").environ.get("MT_XC_DW_FUSED", "1") != "0"   # depthwise data + weight gradient in one kernel (all of Xception's are 3x3 stride 1): config 5 200.0 -> 193.5 ms; 0 = two kernels on two streams
-XC_PLAN = __import__("os").environ.get("MT_XC_PLAN", "1") != "0"      # 0: the Xception phases are never recorded (launch plans, plans.py)
+    return SKIP_HALF and POOL_ARG and DW_PLANES
 
 
 class _XceptionFunction(torch.autograd.Function):

@@ -534,7 +534,7 @@ def test_a_forward_at_another_batch_size_leaves_a_pending_backward_alone():
     m, _ = _model(5, True)
     scope16, scope8 = effnet_engine.planes_scope(m, 16), effnet_engine.planes_scope(m, 8)
     if not any(scope8[0] + scope8[1] + [scope8[2]]):
-        pytest.skip("the plane path is off (MT_EF_PLANES=0 / MT_GEMM_SPLIT=0)")
+        pytest.skip("the plane path is off (MT_GEMM_SPLIT=0)")
     assert scope16 != scope8
     x16, x8 = _input(16, 5).cuda(), _input(8, 6).cuda()
     dfeat = torch.randn(16, 1280, 7, 7, generator=torch.Generator().manual_seed(7)).cuda()

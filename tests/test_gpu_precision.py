@@ -452,7 +452,7 @@ def test_efficientnet_train_step_at_high():
     model = model.cuda()
     scope = effnet_engine.planes_scope(model, n)
     if not any(scope[0] + scope[1] + [scope[2]]):
-        pytest.skip("the plane path is off (MT_EF_PLANES=0 / MT_GEMM_SPLIT=0)")
+        pytest.skip("the plane path is off (MT_GEMM_SPLIT=0)")
     x = synth.clip_inputs(1, n, 1, seed)["videos"].reshape(n, 224, 224, 3).permute(0, 3, 1, 2)
     gw = torch.randn(n, 1280, 7, 7, generator=torch.Generator().manual_seed(7)) * 0.1
     with mintime_amd.matmul_precision("high"):

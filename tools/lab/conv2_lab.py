@@ -1,6 +1,6 @@
 """Lab: Xception conv2's three GEMMs alone at config-5 size (512 crops): forward (im2col K=288 -> 64), data gradient (im2col of dz2, pad 2,
-K=576 -> 32) and weight gradient (64 x 288 over 11 M rows), each timed with events over a few repeats.  MT_CONV_WG64 / MT_FORCE_CFG are
-read by the library at its first launch, so variants are separate processes (tools/lab/conv2_lab.sh)."""
+K=576 -> 32) and weight gradient (64 x 288 over 11 M rows), each timed with events over a few repeats.  Variants (MT_FORCE_CFG,
+MT_WGRAD_BLOCKS_OLD) are separate processes (tools/lab/conv2_lab.sh)."""
 import importlib, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -51,4 +51,4 @@ if "wgrad" in which:
     if os.environ.get("LAB_CMP") and os.path.exists(os.environ["LAB_CMP"]):
         ref = torch.load(os.environ["LAB_CMP"]).double()
         out["wgrad_rel_vs_old_tile"] = float((dw.cpu().double() - ref).norm() / ref.norm())
-print({k: (round(v, 4) if isinstance(v, float) else v) for k, v in out.items()}, "env", {k: os.environ[k] for k in ("MT_CONV_WG64", "MT_FORCE_CFG") if k in os.environ})
+print({k: (round(v, 4) if isinstance(v, float) else v) for k, v in out.items()}, "env", {k: os.environ[k] for k in ("MT_FORCE_CFG", "MT_WGRAD_BLOCKS_OLD") if k in os.environ})
