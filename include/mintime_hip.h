@@ -525,6 +525,34 @@ int mt_adam_multi(const void* items, int count, int64_t total_blocks, float lr, 
                   float eps, float step_size, float bias_correction2_sqrt, int decoupled_weight_decay, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Epoch metrics (next-row f5; csrc/metrics.hip).  The reference moves the logits to the host every step and counts there.
+ * mt_metrics_update: one step's share of check_correct (utils.py:32-57 as called at train.py:367-374, :434-441, test.py:267-277) and of
+ *   `total_loss += round(loss.item(), 2)` (train.py:370, test.py:270), accumulated into device state; one launch of one block, no
+ *   atomics (launches on one stream are serialised: one writer), no host read.  logits [n] fp32; labels [n] fp32, 0 or 1 (non-zero = 1);
+ *   loss [1] fp32 or NULL; mc_labels [n] fp32 or NULL (test.py's multiclass_labels: may be NaN).
+ *   Predicted class = logit > 0.  The reference's round(fp32 sigmoid(logit)) differs only for 0 < logit <~ 1.2e-7, where fp32 sigmoid is
+ *   exactly 0.5 and rounds to 0; logit == 0 and a NaN logit are class 0 under both.
+ *   counts [8] int64 += { n_seen, tp, fp, tn, fn, steps, stored, overflow }: correct = tp + tn, positive_class = tp + fp,
+ *   negative_class = tn + fn.  loss_sums [2] fp64 += { loss, rint(loss * 100) / 100 } in call order (required when loss is given).
+ *   mc_errors [9] int64 (test.py:219; required with mc_labels): [c] += 1 per misclassified sample whose class is an integer in 0..8;
+ *   NaN and any other value are skipped (utils.py:44).  Every (logit, label) is appended to store_scores / store_labels [capacity] at
+ *   the position counts[6], which the kernel reads from the state (no host-side dependence on earlier calls: capturable in a graph);
+ *   what does not fit is dropped and counts[7] is set to 1 -- the counters still count every sample.  The caller zeroes the state.
+ * mt_metrics_auc: the exact area under the ROC curve of the first n stored samples (test.py:280-282 metrics.roc_curve + metrics.auc),
+ *   as integers: out [4] uint64 = { gt, eq, n_pos, n_neg } with gt / eq = the number of (positive i, negative j) pairs with
+ *   score_i > / == score_j, so AUC = (2 gt + eq) / (2 n_pos n_neg) -- equal, in real arithmetic, to the trapezoid area with half
+ *   credit for ties.  NaN scores take part in no pair and in neither class count.  It ranks the logits where the reference ranks fp32
+ *   sigmoid(logit): they differ only where distinct logits collapse to one sigmoid value (from about |logit| > 16.6, or closer than
+ *   an ulp).  Tiled all-pairs count, one block partial each, summed by a second launch in index order; no atomics.
+ *   partials: 4 * ceil(n / 256) uint64 of scratch.  n = 0 writes zeros; n > 2^24 returns MT_ERR_UNSUPPORTED (nothing launched).
+ * ------------------------------------------------------------------------------------------------ */
+int mt_metrics_update(const float* logits, const float* labels, const float* loss, const float* mc_labels, int64_t* counts,
+                      double* loss_sums, int64_t* mc_errors, float* store_scores, unsigned char* store_labels, int64_t capacity,
+                      int n, void* stream);
+int mt_metrics_auc(const float* store_scores, const unsigned char* store_labels, int64_t n, uint64_t* partials, uint64_t* out,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Xception (config 5 extractor, reference models/xception.py).  Dense convolutions are mt_gemm with the IM2COL
  * prologue; separable convolutions are mt_dwconv_* (act 0/2) + mt_gemm; the rest:
  * ------------------------------------------------------------------------------------------------ */

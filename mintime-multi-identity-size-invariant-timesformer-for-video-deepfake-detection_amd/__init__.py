@@ -23,6 +23,8 @@ from . import baseline  # noqa: F401,E402
 from .baseline import Baseline  # noqa: F401,E402
 from . import slowfast, slowfast_engine  # noqa: F401,E402
 from .slowfast import SlowFast, slowfast_r50, slowfast_input_transform  # noqa: F401,E402
+from . import metrics  # noqa: F401,E402
+from .metrics import EpochMetrics  # noqa: F401,E402
 
 __all__ = ["arch", "synth", "lib", "timesformer", "tsf_engine", "SizeInvariantTimeSformer", "efficientnet", "effnet_engine", "EfficientNet",
-           "baseline", "Baseline", "slowfast", "SlowFast", "slowfast_r50", "slowfast_input_transform", "set_matmul_precision", "get_matmul_precision", "matmul_precision"]
+           "baseline", "Baseline", "slowfast", "SlowFast", "slowfast_r50", "slowfast_input_transform", "metrics", "EpochMetrics", "set_matmul_precision", "get_matmul_precision", "matmul_precision"]

@@ -94,13 +94,33 @@ def forward(ef, tsf, batch):
                identities_mask=batch["identities_mask"], positions=batch["positions"])   # train.py:355
 
 
-def train_step(ef, tsf, optimizer, batch, reducer=None, pos_weight=None):
+def _update_metrics(metrics, y_pred, batch_or_labels, loss):
+    """train.py:369-374 / test.py:270-277 on the device: `metrics` is a metrics.EpochMetrics."""
+    if isinstance(batch_or_labels, dict):
+        labels = batch_or_labels["labels"]
+        mc = batch_or_labels.get("multiclass_labels") if metrics.multiclass else None
+    else:
+        labels, mc = batch_or_labels, None
+    metrics.update(y_pred, labels, loss, mc)
+
+
+def _eval_metrics(metrics, out, batch_or_labels):
+    """test.py:269-277: the eval loss (plain BCE-with-logits) and the counters, for an eval step that was given `metrics`."""
+    y_pred = out[0] if isinstance(out, tuple) else out
+    labels = batch_or_labels["labels"] if isinstance(batch_or_labels, dict) else batch_or_labels
+    _update_metrics(metrics, y_pred, batch_or_labels, optim.bce_with_logits(y_pred, labels))
+
+
+def train_step(ef, tsf, optimizer, batch, reducer=None, pos_weight=None, *, metrics=None):
     """One optimisation step (train.py:367-378).  The loss stays on the device (the reference moves the logits to the
-    CPU first, one D2H sync per step, train.py:367)."""
+    CPU first, one D2H sync per step, train.py:367).  metrics: a metrics.EpochMetrics that takes the step's counters and loss
+    (train.py:369-374) in one more launch, without a host read; None = nothing is added to the step."""
     y_pred = forward(ef, tsf, batch)
     if isinstance(y_pred, tuple):
         y_pred = y_pred[0]
     loss = optim.bce_with_logits(y_pred, batch["labels"], pos_weight)          # value + gradient in one launch, on the device
+    if metrics is not None:
+        _update_metrics(metrics, y_pred, batch, loss)
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     if reducer is not None:
@@ -110,9 +130,13 @@ def train_step(ef, tsf, optimizer, batch, reducer=None, pos_weight=None):
 
 
 @torch.no_grad()
-def eval_step(ef, tsf, batch):
-    """test.py:235-247 / predict.py:401-406: eval forward; returns logits (and attentions if the model was built with them)."""
-    return forward(ef, tsf, batch)
+def eval_step(ef, tsf, batch, *, metrics=None):
+    """test.py:235-247 / predict.py:401-406: eval forward; returns logits (and attentions if the model was built with them).
+    metrics: a metrics.EpochMetrics; the step then also computes the loss against batch["labels"] and updates it (test.py:269-277)."""
+    out = forward(ef, tsf, batch)
+    if metrics is not None:
+        _eval_metrics(metrics, out, batch)
+    return out
 
 
 def baseline_forward(ex, model, batch, freeze_backbone=False):
@@ -129,10 +153,13 @@ def baseline_forward(ex, model, batch, freeze_backbone=False):
     return torch.mean(y_pred.reshape(-1, f), 1).unsqueeze(1)                   # train.py:352 (num-frames = f)
 
 
-def baseline_train_step(ex, model, optimizer, batch, pos_weight=None, freeze_backbone=False):
-    """One `--model 0` optimisation step (train.py:341-378); the optimizer comes from make_optimizer(cfg, ex, model)."""
+def baseline_train_step(ex, model, optimizer, batch, pos_weight=None, freeze_backbone=False, *, metrics=None):
+    """One `--model 0` optimisation step (train.py:341-378); the optimizer comes from make_optimizer(cfg, ex, model).
+    metrics: as in train_step."""
     y_pred = baseline_forward(ex, model, batch, freeze_backbone)
     loss = optim.bce_with_logits(y_pred, batch["labels"], pos_weight)
+    if metrics is not None:
+        _update_metrics(metrics, y_pred, batch, loss)
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     optimizer.step()
@@ -140,9 +167,12 @@ def baseline_train_step(ex, model, optimizer, batch, pos_weight=None, freeze_bac
 
 
 @torch.no_grad()
-def baseline_eval_step(ex, model, batch):
-    """test.py:235-244 with `--model 0`: eval forward, frame-averaged logits [B, 1]."""
-    return baseline_forward(ex, model, batch)
+def baseline_eval_step(ex, model, batch, *, metrics=None):
+    """test.py:235-244 with `--model 0`: eval forward, frame-averaged logits [B, 1].  metrics: as in eval_step."""
+    out = baseline_forward(ex, model, batch)
+    if metrics is not None:
+        _eval_metrics(metrics, out, batch)
+    return out
 
 
 def input_gradient(ex, model, batch, pos_weight=None):
@@ -185,12 +215,15 @@ def build_slowfast(seed=0, device="cuda", head_pool_kernel_sizes=((8, 7, 7), (32
     return model, opt
 
 
-def slowfast_train_step(model, optimizer, videos, labels, pos_weight=None, **transform):
+def slowfast_train_step(model, optimizer, videos, labels, pos_weight=None, *, metrics=None, **transform):
     """One `--model 2` optimisation step (train.py:356-378): input transform, forward, BCE-with-logits, SGD.  videos [B, F, H, W, 3]
-    (uint8 or fp32), labels [B]; `transform` goes to slowfast_input_transform (crop_size, side_size, num_frames, interpolation)."""
+    (uint8 or fp32), labels [B]; `transform` goes to slowfast_input_transform (crop_size, side_size, num_frames, interpolation).
+    metrics: as in train_step."""
     x = _slowfast.slowfast_input_transform(videos, **transform)
     y_pred = model(x)
     loss = optim.bce_with_logits(y_pred, labels, pos_weight)
+    if metrics is not None:
+        _update_metrics(metrics, y_pred, labels, loss)
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     optimizer.step()
@@ -198,9 +231,15 @@ def slowfast_train_step(model, optimizer, videos, labels, pos_weight=None, **tra
 
 
 @torch.no_grad()
-def slowfast_eval_step(model, videos, **transform):
-    """test.py:255-259 with `--model 2`: transform (`transform` goes to slowfast_input_transform) and eval forward; returns the logits."""
-    return model(_slowfast.slowfast_input_transform(videos, **transform))
+def slowfast_eval_step(model, videos, *, metrics=None, labels=None, **transform):
+    """test.py:255-259 with `--model 2`: transform (`transform` goes to slowfast_input_transform) and eval forward; returns the logits.
+    metrics: a metrics.EpochMetrics, updated with the logits, `labels` [B] (then required) and the eval loss (test.py:269-277)."""
+    out = model(_slowfast.slowfast_input_transform(videos, **transform))
+    if metrics is not None:
+        if labels is None:
+            raise ValueError("slowfast_eval_step: metrics needs labels")
+        _eval_metrics(metrics, out, labels)
+    return out
 
 
 def slowfast_input_gradient(model, videos, labels, pos_weight=None, **transform):

@@ -145,6 +145,8 @@ PROTOTYPES = {
     "mt_sgd_multi": [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_void_p],
     "mt_adam_multi": [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_float,
                       C.c_int, C.c_void_p],
+    "mt_metrics_update": [f32p, f32p, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, i64, C.c_int, C.c_void_p],
+    "mt_metrics_auc": [f32p, C.c_void_p, i64, C.c_void_p, C.c_void_p, C.c_void_p],
     "mt_conv1x1_wgrad_supported": [C.c_int, C.c_int],
     "mt_conv1x1_wgrad": [f32p] * 7 + [C.c_int, f32p, C.c_int64, C.c_int, C.c_int, C.c_void_p],
     "mt_conv1x1_wgrad_wide_supported": [C.c_int, C.c_int],
