@@ -553,6 +553,49 @@ int mt_metrics_auc(const float* store_scores, const unsigned char* store_labels,
                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Identity clustering (next-row f6; csrc/identity.hip).  The reference copies a video's FaceNet embeddings to the host, takes
+ * np.dot(E, E.T) (preprocessing/cluster_faces.py:96, predict.py:162) and hands it to _generate_connected_components
+ * (preprocessing/utils.py:16-29, called at cluster_faces.py:101 and predict.py:167 with threshold 0.45): a Python double loop over all
+ * n^2 entries that adds the edge (i, j) to a networkx graph wherever i != j and similarities[i, j] > threshold, then lists the
+ * connected components.  The rule, for one video with faces 0..n-1:
+ *   similarity  s_ij = sum_k e_ik * e_jk in fp32, no normalisation, ascending k as one fma chain (v_mfma_f32_32x32x2_f32): s_ij and
+ *               s_ji are the same bits;
+ *   edge        i -- j iff i != j and s_ij > threshold (strict; a NaN similarity is no edge); never across videos;
+ *   label       -1 for a face without an edge (the reference never adds it to the graph: the dataset's discarded faces); otherwise the
+ *               0-based rank of its connected component among the video's components ordered by smallest member -- the order in
+ *               which nx.connected_components yields them for that graph (networkx keeps nodes in insertion order, and the loop
+ *               first touches a component at the row of its smallest member when the matrix is symmetric, as a Gram matrix is).
+ * A batch is ragged: offsets [V + 1] int32 (device), video v owns rows offsets[v] .. offsets[v + 1] - 1 of the T rows.
+ * Limits, checked before anything is launched or written: 1 <= max_faces <= 4096 (a video's labels live in LDS) and 1 <= D <= 2048,
+ * else MT_ERR_UNSUPPORTED; V >= 1, T >= 0.  A video with 0 faces is legal (no tile, n_identities = 0).
+ * err_flag (optional, device int32, sticky, as in mt_embed_fwd): bit 0 = a video has more than max_faces faces -- it is treated as
+ * truncated to its first max_faces (the faces past them are labelled -1) and no access leaves the T rows or the W words; bit 1 = the
+ * label loop hit its trip bound (cannot happen on a symmetric adjacency; a defect must not become a hang); bit 2 = offsets outside
+ * [0, T] (that video is skipped).
+ * mt_identity_adjacency: adj [T][W] uint32, W = ceil(max_faces / 32): bit j & 31 of word j >> 5 of row offsets[v] + i is the edge
+ *   i -- j of video v; the bits past a video's faces are written as zero and every row of a (truncated) video is written whole.
+ *   32 x 32 tiles of each video's Gram matrix, one wavefront each, compared in the accumulator registers and packed with wave ballots;
+ *   no [n, n] float matrix is written.  Both triangles are computed, with the same k order: adj is symmetric.  Block b is a tile of
+ *   the video with tile_prefix[v] <= b < tile_prefix[v + 1], tile_prefix [V + 1] int32 (device) = running sum of
+ *   ceil(min(n_v, max_faces) / 32)^2, total_tiles = its last entry = the grid.
+ * mt_identity_adjacency_sim: the same bit matrix, [n][ceil(n / 32)], from a ready similarity matrix sim [n, n] fp32 of ONE video (the
+ *   reference function's own argument; need not be symmetric): i -- j iff i != j and (sim[i][j] > threshold or sim[j][i] > threshold)
+ *   -- the reference visits both orders and its graph is undirected.  n <= 4096.  source [n] int32: 1 where row i itself holds an
+ *   entry above the threshold.  For an asymmetric matrix the reference's loop first touches a component at its smallest SOURCE, not
+ *   at its smallest member, and that decides the order in which the components are listed.
+ * mt_identity_components: one block per video over adj (row pitch W = ceil(max_faces / 32), which must be symmetric): labels [T] int32
+ *   as above, n_identities [V] int32, sizes [T] int32 or NULL: sizes[offsets[v] + k] = members of identity k of video v, 0 for
+ *   k >= n_identities[v].  source [T] int32 or NULL: with it, components are ranked by their smallest member that is a source (the
+ *   order of the reference on an asymmetric matrix); NULL ranks by smallest member.  Minimum-label propagation + pointer jumping until a round changes nothing, at most n + 1 rounds; the
+ *   result is the unique minimum-member labelling whatever the schedule.  Integer atomics only.
+ * ------------------------------------------------------------------------------------------------ */
+int mt_identity_adjacency(const float* emb, const int* offsets, const int* tile_prefix, int V, int T, int D, int total_tiles,
+                          int max_faces, float threshold, uint32_t* adj, int* err_flag, void* stream);
+int mt_identity_adjacency_sim(const float* sim, int n, float threshold, uint32_t* adj, int* source, void* stream);
+int mt_identity_components(const uint32_t* adj, const int* offsets, const int* source, int V, int T, int max_faces, int* labels,
+                           int* n_identities, int* sizes, int* err_flag, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Xception (config 5 extractor, reference models/xception.py).  Dense convolutions are mt_gemm with the IM2COL
  * prologue; separable convolutions are mt_dwconv_* (act 0/2) + mt_gemm; the rest:
  * ------------------------------------------------------------------------------------------------ */

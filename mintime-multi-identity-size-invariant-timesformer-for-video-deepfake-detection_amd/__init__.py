@@ -25,6 +25,9 @@ from . import slowfast, slowfast_engine  # noqa: F401,E402
 from .slowfast import SlowFast, slowfast_r50, slowfast_input_transform  # noqa: F401,E402
 from . import metrics  # noqa: F401,E402
 from .metrics import EpochMetrics  # noqa: F401,E402
+from . import identities  # noqa: F401,E402
+from .identities import ClusterPlan, IdentityClusters, cluster_embeddings, cluster_similarities, identities_from_labels  # noqa: F401,E402
 
 __all__ = ["arch", "synth", "lib", "timesformer", "tsf_engine", "SizeInvariantTimeSformer", "efficientnet", "effnet_engine", "EfficientNet",
-           "baseline", "Baseline", "slowfast", "SlowFast", "slowfast_r50", "slowfast_input_transform", "metrics", "EpochMetrics", "set_matmul_precision", "get_matmul_precision", "matmul_precision"]
+           "baseline", "Baseline", "slowfast", "SlowFast", "slowfast_r50", "slowfast_input_transform", "metrics", "EpochMetrics", "identities", "ClusterPlan", "IdentityClusters",
+           "cluster_embeddings", "cluster_similarities", "identities_from_labels", "set_matmul_precision", "get_matmul_precision", "matmul_precision"]

@@ -147,6 +147,11 @@ PROTOTYPES = {
                       C.c_int, C.c_void_p],
     "mt_metrics_update": [f32p, f32p, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, i64, C.c_int, C.c_void_p],
     "mt_metrics_auc": [f32p, C.c_void_p, i64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mt_identity_adjacency": [f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                              C.c_void_p, C.c_void_p],
+    "mt_identity_adjacency_sim": [f32p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mt_identity_components": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p],
     "mt_conv1x1_wgrad_supported": [C.c_int, C.c_int],
     "mt_conv1x1_wgrad": [f32p] * 7 + [C.c_int, f32p, C.c_int64, C.c_int, C.c_int, C.c_void_p],
     "mt_conv1x1_wgrad_wide_supported": [C.c_int, C.c_int],

@@ -8,6 +8,7 @@ reference's source enters the repo: the fixtures are inputs' checksums and outpu
     python tools/make_golden.py            # writes every fixture
     GOLDEN_ONLY=baseline python tools/make_golden.py   # only baseline_head.npz and baseline_e2e_train.npz (`--model 0`)
     GOLDEN_ONLY=patches python tools/make_golden.py    # only tsf_p16.npz and tsf_p64.npz (num-patches 16 and 64)
+    GOLDEN_ONLY=identities python tools/make_golden.py # only identity_components.json (the face clustering's connected components)
 """
 import json
 import os
@@ -336,6 +337,81 @@ def slots_case(name):
     print("wrote f1_constants.json")
 
 
+def identity_cases():
+    """(name, threshold, similarity matrix fp32) for identity_case().  Every entry is a multiple of 1/64 (exact in fp32 and short in
+    JSON), so thresholds of 0.5 and 0.75 meet entries that equal them; 0.8 and 0.45 are not fp32 numbers and no entry can equal their
+    fp32 roundings either, so the comparison is the same in fp32 and fp64."""
+    rng = np.random.Generator(np.random.Philox(key=[66, 6]))
+    q = lambda a: (np.asarray(a, dtype=np.float64) / 64.0).astype(np.float32)
+
+    def planted(n, pairs, low=40, asym=False):
+        m = rng.integers(0, low, (n, n))
+        if not asym:
+            m = np.triu(m) + np.triu(m, 1).T
+        for i, j in pairs:
+            m[i, j] = rng.integers(52, 64)
+            if not asym:
+                m[j, i] = m[i, j]
+        np.fill_diagonal(m, 64)
+        return q(m)
+
+    def random_pairs(n, k):
+        return [tuple(int(x) for x in rng.choice(n, 2, replace=False)) for _ in range(k)]
+
+    cases = [("one_face", 0.75, q([[64]])),
+             ("two_joined", 0.75, q([[64, 60], [60, 64]])),
+             ("two_apart", 0.75, q([[64, 10], [10, 64]])),
+             ("blocks", 0.75, planted(12, [(0, 7), (7, 3), (1, 2), (2, 11), (4, 9), (5, 6), (6, 10), (10, 8)])),
+             ("edgeless_faces", 0.75, planted(15, [(2, 9), (9, 13), (4, 5), (11, 1)])),
+             ("late_smallest_member", 0.75, planted(10, [(8, 9), (9, 1), (3, 7), (2, 6), (6, 0)]))]
+    a = planted(6, [], asym=True)
+    a[0, 3], a[3, 0], a[4, 1], a[1, 4], a[5, 2], a[2, 5] = 0.9375, 0.125, 0.0625, 0.875, 0.25, 0.25      # one order each; 5-2 neither
+    cases.append(("asymmetric", 0.75, a))
+    t = planted(8, [(0, 1)])
+    t[2, 3] = t[3, 2] = 0.75                      # exactly the threshold: no edge
+    t[4, 5], t[5, 4] = 0.75, 0.765625             # one order at the threshold, the other one step above: an edge
+    t[6, 7] = t[7, 6] = 0.765625
+    cases.append(("at_threshold", 0.75, t))
+    cases.append(("at_threshold_half", 0.5, q(np.where(np.eye(9, dtype=bool), 64, 32))))
+    m = planted(6, [(0, 5)])
+    m[1, 2], m[2, 1] = np.nan, 0.9375             # NaN one way, above the other way: an edge
+    m[3, 4], m[4, 3] = np.nan, 0.125              # NaN one way, below the other way: none
+    cases.append(("nan_entries", 0.75, m))
+    cases.append(("all_nan", 0.75, np.full((4, 4), np.nan, np.float32)))
+    cases.append(("zero_matrix_negative_threshold", -0.25, np.zeros((7, 7), np.float32)))
+    cases.append(("zero_matrix_zero_threshold", 0.0, np.zeros((5, 5), np.float32)))
+    perm = rng.permutation(40)
+    cases.append(("chain_in_order", 0.75, planted(40, [(i, i + 1) for i in range(39)])))
+    cases.append(("chain_permuted", 0.75, planted(40, [(int(perm[i]), int(perm[i + 1])) for i in range(39)])))
+    cases.append(("two_chains_interleaved", 0.75, planted(33, [(i, i + 2) for i in range(31)])))
+    for n, k, thr in ((5, 2, 0.8), (17, 6, 0.8), (32, 10, 0.45), (33, 12, 0.8), (40, 14, 0.8), (40, 30, 0.45)):
+        cases.append((f"random_n{n}_k{k}", thr, planted(n, random_pairs(n, k), low=28)))
+    cases.append(("random_asymmetric", 0.8, planted(24, random_pairs(24, 9), asym=True)))
+    cases.append(("dense", 0.5, q(rng.integers(0, 64, (20, 20)))))
+    return cases
+
+
+def identity_case(name):
+    """preprocessing/utils.py:16-29 _generate_connected_components run on small similarity matrices: the matrices and the component
+    lists it returns (each sorted, in the order returned) are the fixture."""
+    placeholder_modules("torchvision", "torchvision.transforms")
+    ref = import_reference_file("_ref_preprocessing_utils", os.path.join("preprocessing", "utils.py"))
+    rows = []
+    for case, thr, sim in identity_cases():
+        assert sim.dtype == np.float32 and sim.shape[0] == sim.shape[1] <= 40
+        finite = sim[np.isfinite(sim)].astype(np.float64)
+        assert not np.any(finite == float(np.float32(thr))) or float(np.float32(thr)) == thr, case
+        comps = [sorted(int(i) for i in c) for c in ref._generate_connected_components(sim, thr)]
+        rows.append(dict(name=case, n=int(sim.shape[0]), threshold=thr,
+                         similarities=[[None if np.isnan(x) else float(x) for x in r] for r in sim], components=comps))
+    os.makedirs(OUT, exist_ok=True)
+    path = os.path.join(OUT, name + ".json")
+    with open(path, "w") as fh:
+        json.dump(rows, fh, separators=(",", ":"), allow_nan=False)
+        fh.write("\n")
+    print(f"wrote {path} ({len(rows)} cases, {os.path.getsize(path) / 1024:.0f} KiB)")
+
+
 def e2e_case(EF, TSF, name, batch, frames, identities, ragged, training, seed):
     """Whole step.  Stored twice: the reference in fp32 (what a user would run) and in fp64 (its exact arithmetic;
     the fp32 run of an ill-conditioned case -- train-mode BN over a batch with padded all-zero crops -- deviates from
@@ -593,6 +669,9 @@ GRAD_KEYS_XC = ["conv1.weight", "bn1.weight", "conv2.weight", "bn2.bias", "block
 
 
 def main():
+    if os.environ.get("GOLDEN_ONLY", "") == "identities":       # needs none of the reference's models
+        identity_case("identity_components")
+        return
     torch.manual_seed(0)
     torch.set_num_threads(os.cpu_count())
     EF, TSF = import_reference()
