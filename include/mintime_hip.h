@@ -765,6 +765,48 @@ int mt_sf_ingest_resize_bwd(const float* dout, const float* dout2, const int* fs
 int mt_sf_stem_dgrad(const float* dz, int64_t ldz, const float* wt, float* dx, int N, int T, int H, int W, int kt, int K, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * FaceNet InceptionResnetV1, inference only (the embedder in front of the identity clustering: reference predict.py:150-158,
+ * preprocessing/cluster_faces.py:84-92; csrc/facenet.hip).  Activations are channels-last rows, [N][H][W] rows of C floats with a row
+ * pitch (ld*, in floats), so a branch's last convolution and the pooling branches write their channel slice of the concatenation
+ * buffer in place.  BatchNorm is folded into the weights and a bias by the caller.  No entry point issues an atomic; every sum runs in
+ * an order fixed by the layer's own geometry (C, K, kh, kw, Ho, Wo, stride, padding) and NEVER by N: a face's rows are the same bits
+ * whoever shares its batch.  Row offsets are 64-bit; row counts stay below 2^31.
+ *
+ * mt_conv2d_fwd: Conv2d as an implicit GEMM on v_mfma_f32_32x32x2_f32, any (kh, kw), per-axis stride and padding.
+ *     conv[m][co] = sum_{tap, ci} x[in(m, tap)][ci] * w[co][tap][ci]      (w = torch weight permuted to [K][kh][kw][C]; zero padding)
+ *     y = act(conv + bias)                        res == NULL
+ *     y = act(res + res_scale * (conv + bias))    res given (rows of K floats, pitch ldr): the Inception-ResNet block tail
+ *   act 0 = none, 1 = ReLU; bias [K] or NULL.  One block owns a 64 x 64 output tile and walks the whole reduction in ascending
+ *   (tap, ci) order, 32 per step, each step 16 MFMAs of depth 2: the result is a chain of fused multiply-adds with one rounding per
+ *   product, |y - exact| <= (kh kw C + 4) 2^-24 (|res| + |res_scale| (sum |x w| + |bias|)) to first order.
+ *   C % 4 == 0, K % 4 == 0, pitches % 4 == 0 and >= the widths, x and w 16-byte aligned, else MT_ERR_UNSUPPORTED (the 3-channel stem
+ *   takes a 4th, zero, channel: mt_face_ingest writes it).  Ho, Wo must equal floor((in + 2 p - k) / s) + 1, else MT_ERR_ARG.
+ *   Nothing is launched or written on an error.  y may alias neither x nor res.
+ * mt_face_ingest: src [T][H][W][3] uint8 (is_u8) or fp32 with ELEMENT strides (st, sh, sw, sc) -- a channels-last crop array, or
+ *   the NCHW tensor of the reference's call -- -> out [T][H][W][4] fp32, 16-byte aligned: (u - 127.5) / 128 (standardize; both steps
+ *   are exact for uint8) or u, the 4th channel 0.
+ * mt_maxpool2d_fwd: MaxPool2d(k = 3, s = 2, p = 0) of x [N][H][W] rows (pitch ldx) into y [N][Ho][Wo] rows (pitch ldy), C % 4 == 0,
+ *   both 16-byte aligned; any other (k, s, p) returns MT_ERR_UNSUPPORTED.
+ * mt_avgpool_rows: y[n][c] = (x[n*rows][c] + ... + x[n*rows + rows - 1][c]) / rows, added in that order (AdaptiveAvgPool2d(1)).
+ * mt_l2_normalize_rows: y[r] = x[r] / max(||x[r]||_2, eps) (F.normalize); a zero row stays zero.  One wavefront per row, the sum of
+ *   squares as 64 strided chains joined by a fixed butterfly.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+  int N, H, W, C;                 /* input grid and channels */
+  int Ho, Wo, K;                  /* output grid and channels */
+  int kh, kw, sh, sw, ph, pw;     /* kernel, stride, padding per axis */
+  int act;                        /* 0 none, 1 ReLU */
+  float res_scale;                /* multiplies conv + bias when res is given */
+  int64_t ldx, ldy, ldr;          /* row pitches (floats) of x, y and res */
+} mt_conv2d_desc;
+int mt_conv2d_fwd(const mt_conv2d_desc* d, const float* x, const float* w, const float* bias, const float* res, float* y, void* stream);
+int mt_face_ingest(const void* src, int is_u8, int64_t st, int64_t sh, int64_t sw, int64_t sc, int T, int H, int W, int standardize,
+                   float* out, void* stream);
+int mt_maxpool2d_fwd(const float* x, int64_t ldx, float* y, int64_t ldy, int N, int H, int W, int C, int k, int s, int p, void* stream);
+int mt_avgpool_rows(const float* x, int64_t ldx, float* y, int64_t ldy, int N, int rows, int C, void* stream);
+int mt_l2_normalize_rows(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int D, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Launch plans (the caller side of the step: reference train.py:332-378, the Python loop that issues every op).
  * A plan holds the SEQUENCE of entry-point calls of one phase (EfficientNet forward, TimeSformer forward, TimeSformer backward,
  * EfficientNet backward) so that the host issues a phase with one call instead of hundreds through its FFI.

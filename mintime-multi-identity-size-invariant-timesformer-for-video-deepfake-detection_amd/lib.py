@@ -30,6 +30,12 @@ class Conv3dDesc(C.Structure):
                                        "pw")] + [("ldx", i64), ("ldy", i64)]
 
 
+class Conv2dDesc(C.Structure):
+    """mt_conv2d_desc (include/mintime_hip.h, FaceNet InceptionResnetV1)."""
+    _fields_ = [(n, C.c_int) for n in ("N", "H", "W", "C", "Ho", "Wo", "K", "kh", "kw", "sh", "sw", "ph", "pw", "act")] + \
+               [("res_scale", C.c_float), ("ldx", i64), ("ldy", i64), ("ldr", i64)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("op", C.c_int), ("prologue", C.c_int), ("epilogue", C.c_int),
                 ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
@@ -190,6 +196,11 @@ PROTOTYPES = {
     "mt_sf_ingest_resize_bwd": [f32p, f32p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, f32p] * 2 + [C.c_int] * 7 +
                                [f32p, i64, i64, i64, i64, i64, C.c_void_p],
     "mt_sf_stem_dgrad": [f32p, i64, f32p, f32p] + [C.c_int] * 6 + [C.c_void_p],
+    "mt_conv2d_fwd": [C.c_void_p, f32p, f32p, f32p, f32p, f32p, C.c_void_p],
+    "mt_face_ingest": [C.c_void_p, C.c_int, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p],
+    "mt_maxpool2d_fwd": [f32p, i64, f32p, i64] + [C.c_int] * 7 + [C.c_void_p],
+    "mt_avgpool_rows": [f32p, i64, f32p, i64, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "mt_l2_normalize_rows": [f32p, i64, f32p, i64, i64, C.c_int, C.c_float, C.c_void_p],
     "mt_plan_create": [C.POINTER(C.c_void_p)],
     "mt_plan_destroy": [C.c_void_p],
     "mt_plan_record_begin": [C.c_void_p],
