@@ -21,7 +21,6 @@
 #include "../../include/mintime_hip.h"
 #include "common.hpp"
 #include "planes.hpp"
-#include "rc.hpp"
 #include <stdlib.h>
 
 using namespace mt;
@@ -41,15 +40,11 @@ __device__ __forceinline__ void atomic_add_f64(double* p, double v) { atomicAdd(
 // stay in registers across the block's tiles -> one fp64 atomic per channel per block.
 // ACT: input activation applied after the per-channel affine (act_affine4: 0 none, 1 swish [EfficientNet], 2 relu [Xception]).
 // CC : channels per block (16, or 8 for channel counts like Xception's 728 that are not multiples of 16).
-// RC : 0 = zin is the conv's raw input [N,H,W,C]; Cin > 0 = zin is the BLOCK input y [N,H,W,Cin] and the raw input chunk is rebuilt
-//      as y . We^T while the tile is staged (rc.hpp; we = the expand weight [C, Cin]) -- the expanded tensor is not read.
-template <int K, int S, int T, int ACT, int CC, int RC = 0>
+template <int K, int S, int T, int ACT, int CC>
 __global__ __launch_bounds__(256) void dwconv_tiled_kernel(const float* __restrict__ zin, const float* __restrict__ scale,
                                                            const float* __restrict__ shift, const float* __restrict__ w,
                                                            float* __restrict__ zout, double* __restrict__ stats, int slots,
-                                                           int N, int H, int W, int C, int Ho, int Wo, int pad0, int pad1, PlaneRef po,
-                                                           const float* __restrict__ we) {
-  static_assert(RC == 0 || CC == 16, "the recompute yields 16-channel chunks");
+                                                           int N, int H, int W, int C, int Ho, int Wo, int pad0, int pad1, PlaneRef po) {
   constexpr int CQN = CC / 4, NSLOT = 256 / CQN;
   constexpr int IH = (T - 1) * S + K;
   constexpr int IWP = IH | 1;
@@ -87,22 +82,19 @@ __global__ __launch_bounds__(256) void dwconv_tiled_kernel(const float* __restri
   constexpr int NSL = 256 / CQN;                           // pixels covered per pass of the block
   constexpr int NL = (IH * IH + NSL - 1) / NSL;            // float4 slots per thread
   static_assert(NL <= 32, "validity mask is 32 bits");
-  // staging role: (pixel slot, channel quad) of the element this thread brings into the LDS tile.  Plain: the compute role's.
-  // RC: the MFMA result layout -- lane l of a wavefront holds pixel (l & 15) of its 16-pixel group, channel quad l >> 4.
-  const int lane = tid & 63;
-  const int f_q = RC ? (lane >> 4) : cq, f_slot = RC ? ((tid >> 6) * 16 + (lane & 15)) : slot;
-  const float4 sc_q = *reinterpret_cast<const float4*>(scale + c0 + f_q * 4);
-  const float4 sh_q = *reinterpret_cast<const float4*>(shift + c0 + f_q * 4);
-  constexpr int RCW = RC ? RC : 8;
-  RcFrag<RCW> wfrag, ypre[RC ? NL : 1];
-  if constexpr (RC > 0) rc_load<RCW>(wfrag, we + (int64_t)(c0 + (lane & 15)) * RC, lane);
-  float4 pre[RC ? 1 : NL];
+  // staging role: the pixel slot of the element this thread brings into the LDS tile -- the compute role's.  It stays a local of its
+  // own: with `slot` written in its place the compiler allocates 130 instead of 128 VGPRs for the 3x3 stride-1 14 x 14 instances
+  // (three wavefronts per SIMD instead of four) and 196 instead of 192 for the 5x5 stride-2 ones.
+  const int f_slot = slot;
+  const float4 sc_q = *reinterpret_cast<const float4*>(scale + c0 + cq * 4);
+  const float4 sh_q = *reinterpret_cast<const float4*>(shift + c0 + cq * 4);
+  float4 pre[NL];
   unsigned pre_ok = 0;
   auto fetch = [&](int64_t tile) {
     int n, ty, tx;
     tile_nyx(tile, ty_n, tx_n, n, ty, tx);
     const int ih0 = ty * T * S - pad0, iw0 = tx * T * S - pad1;      // TF-SAME pads each axis by its own size
-    const float* img = RC ? zin + (int64_t)n * H * W * RC : zin + (int64_t)n * H * W * C + c0 + cq * 4;
+    const float* img = zin + (int64_t)n * H * W * C + c0 + cq * 4;
     pre_ok = 0;
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
@@ -111,8 +103,7 @@ __global__ __launch_bounds__(256) void dwconv_tiled_kernel(const float* __restri
       const int ih = ih0 + iy, iw = iw0 + ix;
       if (pix < IH * IH && ih >= 0 && ih < H && iw >= 0 && iw < W) pre_ok |= 1u << i;
       const int ihc = min(max(ih, 0), H - 1), iwc = min(max(iw, 0), W - 1);
-      if constexpr (RC > 0) rc_load<RCW>(ypre[i], img + ((int64_t)ihc * W + iwc) * RC, lane);
-      else pre[i] = *reinterpret_cast<const float4*>(img + ((int64_t)ihc * W + iwc) * C);
+      pre[i] = *reinterpret_cast<const float4*>(img + ((int64_t)ihc * W + iwc) * C);
     }
   };
   int64_t tile = tile0;
@@ -125,14 +116,12 @@ __global__ __launch_bounds__(256) void dwconv_tiled_kernel(const float* __restri
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int pix = f_slot + i * NSL;
-      float4 zraw;
-      if constexpr (RC > 0) zraw = rc_mma<RCW>(wfrag, ypre[i]);       // (all lanes: the MFMA runs outside the range test)
-      else zraw = pre[i];
+      const float4 zraw = pre[i];
       if (pix < IH * IH) {
         const int iy = pix / IH, ix = pix - iy * IH;
         const float4 a = act_affine4<ACT>(zraw, sc_q, sh_q);
         const bool ok = (pre_ok >> i) & 1u;
-        *reinterpret_cast<float4*>(lds + (iy * IWP + ix) * CC + f_q * 4) =
+        *reinterpret_cast<float4*>(lds + (iy * IWP + ix) * CC + cq * 4) =
             make_float4(ok ? a.x : 0.f, ok ? a.y : 0.f, ok ? a.z : 0.f, ok ? a.w : 0.f);
       }
     }
@@ -192,10 +181,9 @@ __global__ __launch_bounds__(256) void dwconv_tiled_kernel(const float* __restri
   }
 }
 
-template <int K, int S, int T, int ACT, int CC, int RC = 0>
+template <int K, int S, int T, int ACT, int CC>
 int launch_dw_tiled(const float* zin, const float* scale, const float* shift, const float* w, float* zout, double* stats, int slots,
-                    int N, int H, int W, int C, int Ho, int Wo, int pad0, int pad1, hipStream_t s, const PlaneRef& po,
-                    const float* we = nullptr) {
+                    int N, int H, int W, int C, int Ho, int Wo, int pad0, int pad1, hipStream_t s, const PlaneRef& po) {
   constexpr int IH = (T - 1) * S + K;
   constexpr int IWP = IH | 1;
   size_t lds = (size_t)(IH * IWP * CC + (K > 3 ? K * K * CC : 0)) * sizeof(float);
@@ -203,13 +191,13 @@ int launch_dw_tiled(const float* zin, const float* scale, const float* shift, co
   const int chunks = C / CC;
   const int64_t ntiles = (int64_t)N * ((Ho + T - 1) / T) * ((Wo + T - 1) / T);
   const unsigned bx = xcd_chunk_grid(chunks, ntiles, 8192);
-  auto k = dwconv_tiled_kernel<K, S, T, ACT, CC, RC>;
+  auto k = dwconv_tiled_kernel<K, S, T, ACT, CC>;
   if (lds > 48 * 1024) {
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds);
     if (e != hipSuccess) return fail(MT_ERR_LAUNCH, "mt_dwconv_fwd: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
   }
   hipLaunchKernelGGL(k, dim3(bx), dim3(256), lds, s, zin, scale, shift, w, zout, stats, slots != 0 ? slots : 1, N, H,
-                     W, C, Ho, Wo, pad0, pad1, po, we);
+                     W, C, Ho, Wo, pad0, pad1, po);
   return check_launch("mt_dwconv_fwd(tiled)");
 }
 
@@ -450,35 +438,6 @@ extern "C" int mt_dwconv_fwd(const float* zin, const float* scale, const float* 
   if (!zin || !scale || !shift || !w || !zout) return fail(MT_ERR_ARG, "mt_dwconv_fwd: null pointer");
   return dwconv_fwd(zin, scale, shift, w, zout, stats, slots, N, H, W, C, k, stride, act, (hipStream_t)stream, PlaneRef{nullptr, 0, 0, 0},
                     "mt_dwconv_fwd");
-}
-
-// instances of the recompute form: (k, stride, Cin, output tile) of EfficientNet-B0's blocks 1-3 (the expanded tensors of the 112^2 /
-// 56^2 grids).  5x5 stride 2 takes 7 x 7 tiles: a 14 x 14 tile's 31 x 31 halo is 16 operand fragments of prefetch per thread (occupancy 1).
-#define MT_DW_RC_INSTANCES(X) X(3, 2, 16, 14) X(3, 1, 24, 14) X(5, 2, 24, 7)
-
-extern "C" int mt_dwconv_rc_supported(int cin, int C, int k, int stride, int H) {
-  if (C <= 0 || (C & 15) || (H + stride - 1) / stride < 14) return 0;
-#define MT_CASE(K_, S_, CIN_, T_) if (k == K_ && stride == S_ && cin == CIN_) return 1;
-  MT_DW_RC_INSTANCES(MT_CASE)
-#undef MT_CASE
-  return 0;
-}
-
-extern "C" int mt_dwconv_fwd_rc(const float* y, const float* we, int cin, const float* scale, const float* shift, const float* w,
-                                float* zout, double* stats, int slots, int N, int H, int W, int C, int k, int stride, void* stream) {
-  if (!y || !we || !scale || !shift || !w || !zout) return fail(MT_ERR_ARG, "mt_dwconv_fwd_rc: null pointer");
-  if (((uintptr_t)y | (uintptr_t)we) & 15) return fail(MT_ERR_ARG, "mt_dwconv_fwd_rc: y and we must be 16-byte aligned");
-  if (!mt_dwconv_rc_supported(cin, C, k, stride, H))
-    return fail(MT_ERR_UNSUPPORTED, "mt_dwconv_fwd_rc: no instance for k=%d stride=%d Cin=%d C=%d H=%d", k, stride, cin, C, H);
-  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
-  const int pad = max((Ho - 1) * stride + k - H, 0) / 2, padw = max((Wo - 1) * stride + k - W, 0) / 2;
-  const PlaneRef po{nullptr, 0, 0, 0};
-#define MT_CASE(K_, S_, CIN_, T_)                                                                                              \
-  if (k == K_ && stride == S_ && cin == CIN_)                                                                                  \
-    return launch_dw_tiled<K_, S_, T_, 1, 16, CIN_>(y, scale, shift, w, zout, stats, slots, N, H, W, C, Ho, Wo, pad, padw, (hipStream_t)stream, po, we);
-  MT_DW_RC_INSTANCES(MT_CASE)
-#undef MT_CASE
-  return fail(MT_ERR_UNSUPPORTED, "mt_dwconv_fwd_rc: no instance");
 }
 
 extern "C" int mt_dwconv_fwd_planes(const float* zin, const float* scale, const float* shift, const float* w, void* planes, int N, int H,

@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void conv1x1_rows_kernel(ConvArgs p) {
           if (row < p.rows) {
             float v = acc[j][r];
             if (p.res) v += p.res[row * p.Cout + co];
-            if (p.out) p.out[row * p.Cout + co] = v;        // out == NULL: BatchNorm statistics of the product only
+            p.out[row * p.Cout + co] = v;
             s1[j] += v; s2[j] = fmaf(v, v, s2[j]);
           }
         }
@@ -215,23 +215,20 @@ int launch(const ConvArgs& a, int amode, hipStream_t st) {
 // (measured on the 256-crop batch, us, streaming / GEMM): data gradients 16->32 165/216, 24->96 101/155, 96->16 495/665,
 // 24->144 227/249; forward 24->144 163/186.  Wider k (144, 240 channels in) loses to the GEMM (the register->LDS transpose of a
 // 64 x 144 tile costs more than it hides) and is not instantiated; the gated forward is a tie and stays on the GEMM.
-#define MT_ROWS_INSTANCES(X) X(1, 1, 128) X(1, 3, 128) X(1, 5, 128) X(3, 1, 128)
+#define MT_ROWS_SHAPES(X) X(1, 1, 128) X(1, 3, 128) X(1, 5, 128) X(3, 1, 128)
 
-static bool rows_instance(int Cin, int Cout) {
+static bool rows_shape_built(int Cin, int Cout) {
   if ((Cin & 3) || Cin <= 0 || Cout <= 0) return false;
   const int kt = (Cin + 31) / 32, nt = (Cout + 31) / 32;
 #define MT_CASE(K_, N_, R_) if (kt == K_ && nt == N_) return true;
-  MT_ROWS_INSTANCES(MT_CASE)
+  MT_ROWS_SHAPES(MT_CASE)
 #undef MT_CASE
   return false;
 }
 
-// does mt_conv1x1_rows have an instance for this channel pair at all?  (mt_conv1x1_rows_supported: is it the better choice)
-extern "C" int mt_conv1x1_rows_instance(int Cin, int Cout) { return rows_instance(Cin, Cout) ? 1 : 0; }
-
 // is the streaming kernel the better choice for this conv?  (amode as in mt_conv1x1_rows)
 extern "C" int mt_conv1x1_rows_supported(int Cin, int Cout, int amode) {
-  if (!rows_instance(Cin, Cout)) return 0;
+  if (!rows_shape_built(Cin, Cout)) return 0;
   const int kt = (Cin + 31) / 32, nt = (Cout + 31) / 32;
   if (amode == A_BNBWD) return 1;
   if (amode == A_PLAIN) return kt == 1 && nt == 5;
@@ -241,8 +238,8 @@ extern "C" int mt_conv1x1_rows_supported(int Cin, int Cout, int amode) {
 extern "C" int mt_conv1x1_rows(const float* x, const float* x2, const float* w, int ldw, int w_transposed, const float* c0,
                                const float* c1, const float* c2, int hw, int amode, const float* res, float* out, double* stats,
                                int slots, int64_t rows, int Cin, int Cout, void* stream) {
-  if (!x || !w || (!out && !stats)) return fail(MT_ERR_ARG, "mt_conv1x1_rows: null pointer");
-  if (!rows_instance(Cin, Cout)) return fail(MT_ERR_UNSUPPORTED, "mt_conv1x1_rows: no instance for %d -> %d channels", Cin, Cout);
+  if (!x || !w || !out) return fail(MT_ERR_ARG, "mt_conv1x1_rows: null pointer");
+  if (!rows_shape_built(Cin, Cout)) return fail(MT_ERR_UNSUPPORTED, "mt_conv1x1_rows: no instance for %d -> %d channels", Cin, Cout);
   if (amode == A_GATE && (!c0 || !c1 || !c2 || hw <= 0)) return fail(MT_ERR_ARG, "mt_conv1x1_rows: gate mode needs scale, shift, gate, hw");
   if (amode == A_BNBWD && (!c0 || !c1 || !c2 || !x2)) return fail(MT_ERR_ARG, "mt_conv1x1_rows: BN-backward mode needs ka, kb, kc and z");
   if (amode < 0 || amode > 2) return fail(MT_ERR_ARG, "mt_conv1x1_rows: bad mode");
@@ -251,7 +248,7 @@ extern "C" int mt_conv1x1_rows(const float* x, const float* x2, const float* w, 
   hipStream_t st = (hipStream_t)stream;
   const int kt = (Cin + 31) / 32, nt = (Cout + 31) / 32;
 #define MT_CASE(K_, N_, R_) if (kt == K_ && nt == N_) return launch<K_, N_, R_>(a, amode, st);
-  MT_ROWS_INSTANCES(MT_CASE)
+  MT_ROWS_SHAPES(MT_CASE)
 #undef MT_CASE
   return fail(MT_ERR_UNSUPPORTED, "mt_conv1x1_rows: no instance");
 }

@@ -45,11 +45,6 @@ def _padded_act(zin, scale, shift, N, H, W, k, s, kind):
     return Fn.pad(a, (pw0, pw1, ph0, ph1)), Ho, Wo, ph0, pw0
 
 
-def expand(y, we):
-    """The recompute forms' depthwise input: y [rows, Cin] through the expand weight we [C, Cin]."""
-    return y @ we.t()
-
-
 def dw_fwd(zin, scale, shift, w, N, H, W, k, s, kind):
     """zout [N*Ho*Wo, C], sum zout, sum zout^2 (per channel)."""
     a_pad, _, _, _, _ = _padded_act(zin, scale, shift, N, H, W, k, s, kind)

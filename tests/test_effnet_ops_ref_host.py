@@ -185,10 +185,3 @@ def test_weight_pack_reference_is_the_im2col_operand():
     assert float(wp[:, k * k * Ci:].abs().sum()) == 0.0
     wp[:, k * k * Ci:] = 7.0
     assert torch.equal(R.conv_weight_unpack(wp, Co, Ci, k), w)
-
-
-def test_expand_is_the_1x1_convolution():
-    g = _g(3)
-    y, we = _rn(g, 12, 4), _rn(g, 6, 4)
-    ref = Fn.conv2d(y.reshape(1, 3, 4, 4).permute(0, 3, 1, 2), we.reshape(6, 4, 1, 1)).permute(0, 2, 3, 1).reshape(12, 6)
-    assert rel_err(R.expand(y, we), ref) <= TOL

@@ -1,5 +1,5 @@
 """Per-kernel parity of the frame extractors' hand-written non-GEMM kernels (csrc/effnet_fwd.hip, csrc/effnet_bwd.hip and the weight
-packing of csrc/xception.hip: the depthwise convolution with its two gradients and recompute forms, the BatchNorm bookkeeping, the
+packing of csrc/xception.hip: the depthwise convolution with its two gradients, the BatchNorm bookkeeping, the
 activation adjoint, squeeze-excite, the stem weight gradient) against tests/effnet_ops_ref.py in fp64 on the CPU (tied to torch autograd
 by tests/test_effnet_ops_ref_host.py).  The conventions are those of tests/test_gpu_tsf_ops.py: every test calls the C ABI directly;
 stored outputs start as NaN, accumulated ones (dw, dgamma, dbeta, dw1, dw2, db1, db2) at a canary that the reference adds; outputs sit
@@ -55,10 +55,6 @@ TOL = {
     "dw_bwd.du_in": 8e-7,             # 3.8e-7 (worst image, parts 2 slots 8, k 5 s 1 swish, N 120 7x7 C 1152); yardstick 3.5e-7
     "dw_bwd.sums": 9e-7,              # 4.4e-7 (sum du_in xhat first chunk, parts 2 + residuals, k 3 s 2 swish, N 2 10x10 C 40); yardstick 1.6e-7
     "dw_bwd.dw": 6e-7,                # 2.9e-7 (last chunk, parts 1, k 5 s 1 swish, N 120 7x7 C 1152); yardstick 1.2e-7
-    "rc.zout": 5e-7,                  # 2.4e-7 (first chunk, k 3 s 1 Cin 24 C 48, N 2 14x14); yardstick 1.8e-7
-    "rc.du_in": 5e-7,                 # 2.3e-7 (worst image, k 3 s 1 Cin 24 C 48, N 2 15x17); yardstick 2.3e-7
-    "rc.sums": 5e-7,                  # 2.2e-7 (forward sum z^2 last chunk, slots 8, k 3 s 1 Cin 24 C 32, N 2 14x14); yardstick 1.0e-7
-    "rc.dw": 5e-7,                    # 2.0e-7 (last chunk, slots -8, k 5 s 2 Cin 24 C 48, N 2 30x34); yardstick 1.8e-7
     "se_fwd": 6e-7,                   # 2.6e-7 (hidden, image 1, N 3 HW 49 C 4 CS 5); yardstick 7.6e-8
     "se_bwd.data": 2e-6,              # 5.2e-7 (dpooled, image 0, parts 3, N 3 HW 49 C 4 CS 5); yardstick 3.0e-7
     "se_bwd.wgrad": 5e-7,             # 2.4e-7 (dw1, deterministic, N 35 HW 49 C 144 CS 28); yardstick 2.0e-7
@@ -464,100 +460,7 @@ def test_depthwise_refusals():
     assert b.abs().sum().item() == 0.0 and st.abs().sum().item() == 0.0
 
 
-# ---- 3. the recompute forms ----------------------------------------------------------------------------------------------------------
-
-RC_INSTANCES = [(3, 2, 16), (3, 1, 24), (5, 2, 24)]          # (k, stride, Cin): MT_DW_RC_INSTANCES
-
-
-def test_recompute_instance_table():
-    lib = L.get()
-    for k, s, cin in RC_INSTANCES:
-        for C in (16, 32, 48, 96, 144):
-            assert lib.mt_dwconv_rc_supported(cin, C, k, s, 14 * s) == 1
-            assert lib.mt_dwconv_rc_supported(cin, C, k, s, 14 * s - s) == 0          # Ho 13 < 14
-        assert lib.mt_dwconv_rc_supported(cin, 24, k, s, 56) == 0                     # C % 16 != 0
-        assert lib.mt_dwconv_rc_supported(cin, 0, k, s, 56) == 0
-        for other in (8, 32, 40, 16 if cin == 24 else 24):
-            assert lib.mt_dwconv_rc_supported(other, 96, k, s, 56) == 0               # any other Cin
-    for k, s in ((3, 1), (3, 2), (5, 1), (5, 2)):
-        for cin in (16, 24):
-            assert lib.mt_dwconv_rc_supported(cin, 96, k, s, 56) == int((k, s, cin) in RC_INSTANCES)
-
-
-def test_recompute_refusals():
-    """Host-side checks only: a y or we that is not 16-byte aligned, and a shape outside the instance table."""
-    lib, b, st = L.get(), _scratch(), torch.zeros(1 << 12, dtype=F64, device=dev)
-    p, off, sp, s = L.ptr(b), L.ptr(b[1:]), L.ptr(st), L.stream_ptr()
-    for y, we in ((off, p), (p, off)):
-        assert lib.mt_dwconv_fwd_rc(y, we, 24, p, p, p, p, None, 0, 1, 14, 14, 16, 3, 1, s) == MT_ERR_ARG
-        assert lib.mt_dwconv_bwd_rc(p, p, p, p, y, we, 24, p, p, p, p, sp, 1, p, 1, 14, 14, 16, 3, 1, 2, s) == MT_ERR_ARG
-    assert lib.mt_dwconv_fwd_rc(p, p, 24, p, p, p, p, None, 0, 1, 13, 13, 16, 3, 1, s) == MT_ERR_UNSUPPORTED      # Ho 13
-    assert lib.mt_dwconv_fwd_rc(p, p, 16, p, p, p, p, None, 0, 1, 14, 14, 16, 3, 1, s) == MT_ERR_UNSUPPORTED      # Cin 16 at stride 1
-    assert lib.mt_dwconv_bwd_rc(p, p, p, p, p, p, 24, p, p, p, p, sp, 1, p, 1, 14, 14, 24, 3, 1, 2, s) == MT_ERR_UNSUPPORTED   # C 24
-    assert lib.mt_dwconv_bwd_rc(p, p, p, p, p, p, 24, p, p, p, p, sp, 1, p, 1, 14, 14, 16, 3, 1, 3, s) == MT_ERR_ARG           # parts 3
-    assert lib.mt_dwconv_bwd_rc(p, p, p, p, p, p, 16, p, p, p, p, sp, 1, p, 1, 29, 28, 16, 3, 2, 2, s) == MT_ERR_UNSUPPORTED   # odd H
-    assert b.abs().sum().item() == 0.0 and st.abs().sum().item() == 0.0
-
-
-@pytest.mark.parametrize("Ho,dW", [(14, 0), (15, 2)])
-@pytest.mark.parametrize("C", [32, 48])
-@pytest.mark.parametrize("k,s,cin", RC_INSTANCES)
-def test_recompute_forms_vs_fp64(k, s, cin, C, Ho, dW):
-    """mt_dwconv_fwd_rc and mt_dwconv_bwd_rc (parts 1 and 2) against R.dw_fwd / R.dw_bwd in fp64 on y @ We^T -- independent of the
-    stored-expansion kernels: Ho 14 = full tiles, Ho 15 = partial ones (and W != H)."""
-    N, H = 2, Ho * s
-    W = H + dW * s
-    Wo = -(-W // s)
-    g = _gen(100 * k + 10 * s + C + Ho)
-    y = torch.randn(N * H * W, cin, generator=g)
-    we = torch.randn(C, cin, generator=g) * cin ** -0.5
-    c = _dw_bwd_inputs(N, H, W, C, k, s, 7000 + 100 * k + C + Ho)
-    del c["zin"], c["res_pre"], c["res_post"]
-
-    def refs(dtype):
-        t = {n: v.to(dtype) for n, v in c.items()}
-        zin = R.expand(y.to(dtype), we.to(dtype))
-        return (R.dw_fwd(zin, t["scale"], t["shift"], t["w"], N, H, W, k, s, 1),
-                R.dw_bwd(t["du"], t["z"], t["kabc"], t["w"], zin, t["scale"], t["shift"], t["mi"], N, H, W, k, s, 1))
-
-    def compare(fig, tag, zout, fsums, du_in, bsums, dw, canary):
-        _spatial(fig, "rc.zout", f"mt_dwconv_fwd_rc{tag} zout", zout, ref_f[0], N, Ho, Wo, (k - 1) // 2, 16)
-        _sums(fig, "rc.sums", f"mt_dwconv_fwd_rc{tag} sum z", fsums[0], ref_f[1], 16)
-        _sums(fig, "rc.sums", f"mt_dwconv_fwd_rc{tag} sum z^2", fsums[1], ref_f[2], 16)
-        _dw_bwd_compare(fig, f"mt_dwconv_bwd_rc{tag}", du_in, bsums, dw, ref_b, N, H, W, C, k, ("rc.du_in", "rc.sums", "rc.dw"), canary)
-
-    ref_f, ref_b = refs(F64)
-    what = f"rc k{k} s{s} Cin{cin} C{C} N{N} {H}x{W}"
-    if YARD:
-        yf, yb = refs(torch.float32)
-        compare(_Figures(what, True), " fp32", yf[0], torch.stack(yf[1:]), yb[0], torch.stack(yb[1:3]), yb[3], 0.0)
-    lib = L.get()
-    assert lib.mt_dwconv_rc_supported(cin, C, k, s, H) == 1
-    cd = {n: _d(v) for n, v in c.items()}
-    y_d, we_d = _d(y), _d(we)
-    fig = _Figures(what)
-    out = {}
-    for slots in (8, -8):
-        obuf, zout = _guarded(N * Ho * Wo * C)
-        fbuf, fst = _stats_buffer(slots, C)
-        L.check(lib.mt_dwconv_fwd_rc(L.ptr(y_d), L.ptr(we_d), cin, L.ptr(cd["scale"]), L.ptr(cd["shift"]), L.ptr(cd["w"]), L.ptr(zout),
-                                     L.ptr(fst), slots, N, H, W, C, k, s, L.stream_ptr()), "mt_dwconv_fwd_rc")
-        ibuf, du_in = _guarded(N * H * W * C)
-        bbuf, bst = _stats_buffer(slots, C)
-        wbuf, dw = _guarded(C * k * k, CANARY)
-        for parts in (1, 2):
-            L.check(lib.mt_dwconv_bwd_rc(L.ptr(cd["du"]), L.ptr(cd["z"]), L.ptr(cd["kabc"]), L.ptr(cd["w"]), L.ptr(y_d), L.ptr(we_d), cin,
-                                         L.ptr(cd["scale"]), L.ptr(cd["shift"]), L.ptr(cd["mi"]), L.ptr(du_in), L.ptr(bst), slots,
-                                         L.ptr(dw), N, H, W, C, k, s, parts, L.stream_ptr()), "mt_dwconv_bwd_rc")
-        torch.cuda.synchronize()
-        fig.true(f"slots {slots}: guard bands intact", all(_bands_intact(b) for b in (obuf, fbuf, ibuf, bbuf, wbuf)))
-        compare(fig, f" slots {slots}:", zout, _stats_read(fst, slots, C), du_in, _stats_read(bst, slots, C), dw.reshape(C, 1, k, k), CANARY)
-        out[slots] = (zout, du_in)
-    fig.true("zout and du_in are the same bits in both accumulator modes", torch.equal(out[8][0], out[-8][0]) and torch.equal(out[8][1], out[-8][1]))
-    fig.done()
-
-
-# ---- 4. squeeze-excite forward -------------------------------------------------------------------------------------------------------
+# ---- 3. squeeze-excite forward -------------------------------------------------------------------------------------------------------
 
 SE_C = [4, 40, 96, 144, 1152]                 # block shapes 1 x 256, 10 x 25, 24 x 10, 36 x 7, 48 x 5; 144 = a partial second 128-channel slab
 SE_CS = [4, 5, 6, 10, 20, 28, 48]             # odd CS in the two-halves split, CS % 4 != 0 in the four-row walk, CS > 16: two hidden blocks
@@ -637,7 +540,7 @@ def test_squeeze_excite_forward_refusals():
     assert b.abs().sum().item() == 0.0
 
 
-# ---- 5. mt_se_bwd ------------------------------------------------------------------------------------------------------------------
+# ---- 4. mt_se_bwd ------------------------------------------------------------------------------------------------------------------
 
 SE_BWD_SHAPES = SE_SHAPES + [(19, 49, 40, 10), (35, 49, 144, 28), (19, 9, 1152, 48)]       # N 19 / 35: 16-image chunks with a ragged last one
 _SE_DATA = ("dgate", "dpre2", "dhid", "dpooled")
@@ -724,7 +627,7 @@ def test_squeeze_excite_backward_refusals():
     assert b.abs().sum().item() == 0.0
 
 
-# ---- 6. mt_bn_finalize / mt_bn_bwd_finalize ----------------------------------------------------------------------------------------
+# ---- 5. mt_bn_finalize / mt_bn_bwd_finalize ----------------------------------------------------------------------------------------
 
 def _split_over_slots(total, slots, g):
     """[|slots|][C] fp64 per-slot values that add up to about `total`; returns them and the ABI's buffer holding them (fp64, or the
@@ -855,7 +758,7 @@ def test_batchnorm_backward_finalize_vs_fp64(C, slots, training):
     fig.done()
 
 
-# ---- 7. mt_bn_act_bwd / mt_bn_act_fwd ----------------------------------------------------------------------------------------------
+# ---- 6. mt_bn_act_bwd / mt_bn_act_fwd ----------------------------------------------------------------------------------------------
 
 BN_ACT_CASES = [(act, gate, rs, 258, 49, C, slots) for act in (0, 1, 2) for gate, rs in ((1, 1), (0, 0), (1, 0), (0, 1))
                 for C, slots in ((24, 8), (96, -8))]                       # rows 49 * 5 + 13: no multiple of PB, the last image partial
@@ -935,7 +838,7 @@ def test_activation_forward_vs_fp64(act, with_res, with_rs, rows, C):
     fig.done()
 
 
-# ---- 8. mt_stem_conv_wgrad ---------------------------------------------------------------------------------------------------------
+# ---- 7. mt_stem_conv_wgrad ---------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("H,W,u8,det", [(H, W, u8, False) for H, W in ((8, 12), (9, 13), (6, 224), (6, 258)) for u8 in (0, 1)]
                          + [(8, 12, 0, True), (8, 12, 1, True)])
@@ -988,7 +891,7 @@ def test_stem_weight_gradient_refusals():
     assert b.abs().sum().item() == 0.0
 
 
-# ---- 9. mt_conv_weight_unpack_grad -------------------------------------------------------------------------------------------------
+# ---- 8. mt_conv_weight_unpack_grad -------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("Co,Ci,k,ld", [(32, 3, 3, 28), (64, 32, 3, 288)])
 def test_weight_unpack_inverts_pack(Co, Ci, k, ld):

@@ -105,8 +105,8 @@ def test_package_surface_limits_and_abi_number():
     decl = hdr[hdr.index("Identity clustering"):hdr.index("int mt_identity_components")]
     for cited in ("preprocessing/utils.py:16-29", "cluster_faces.py", "predict.py", "4096", "2048"):
         assert cited in decl
-    assert L.ABI_VERSION == 122
-    assert re.search(r"#define\s+MT_VERSION\s+(\d+)", hdr).group(1) == "122"
+    assert L.ABI_VERSION == 123
+    assert re.search(r"#define\s+MT_VERSION\s+(\d+)", hdr).group(1) == "123"
 
 
 FACES = [(30, 50, 40), (10, 52, 44), (20, 20, 16), (40, 48, 36), (50, 22, 18), (60, 90, 80)]

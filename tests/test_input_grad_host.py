@@ -21,7 +21,7 @@ def test_entry_point_is_declared_and_bound(name):
 
 
 def test_abi_version_did_not_move():
-    assert L.ABI_VERSION == 122 and int(re.search(r"#define\s+MT_VERSION\s+(\d+)", header_text()).group(1)) == 122
+    assert L.ABI_VERSION == 123 and int(re.search(r"#define\s+MT_VERSION\s+(\d+)", header_text()).group(1)) == 123
 
 
 class _NeverCalled(torch.nn.Module):

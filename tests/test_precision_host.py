@@ -20,9 +20,9 @@ def _library():
     lib.set_matmul_precision("highest")
 
 
-def test_abi_version_is_122_in_header_binding_and_library():
-    assert lib.ABI_VERSION == lib.header_version() == 122
-    assert lib.get().mt_version() == 122
+def test_abi_version_agrees_in_header_binding_and_library():
+    assert lib.ABI_VERSION == lib.header_version() == 123
+    assert lib.get().mt_version() == 123
     assert "mt_gemm_set_precision" in lib.PROTOTYPES and "mt_gemm_get_precision" in lib.PROTOTYPES
 
 
