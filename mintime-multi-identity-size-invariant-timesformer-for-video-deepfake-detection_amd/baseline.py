@@ -61,8 +61,7 @@ class _BaselineHeadFunction(torch.autograd.Function):
         pooled = torch.empty(n, C, dtype=torch.float32, device=dev) if save else None
         part = torch.empty(n * ((C + 255) // 256), dtype=torch.float32, device=dev)
         logits = torch.empty(n, 1, dtype=torch.float32, device=dev)
-        L.check(L.get().mt_baseline_head_fwd(L.ptr(x), layout, n, hw, C, m, L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), L.ptr(vc),
-                                             L.ptr(pooled), L.ptr(part), L.ptr(logits), L.stream_ptr()), "mt_baseline_head_fwd")
+        L.mt.baseline_head_fwd(x, layout, n, hw, C, m, w1, b1, w2, b2, vc, pooled, part, logits)
         ctx.model, ctx.dims, ctx.params, ctx.x_shape = model, (layout, n, hw, C, m), (w1, b1, w2, b2), x.shape
         ctx.saved = dict(pooled=pooled, vc=vc, stamp=plans.stamp((w1, b1, w2, b2))) if save else None
         return logits
@@ -85,9 +84,7 @@ class _BaselineHeadFunction(torch.autograd.Function):
         dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dev) if need_x else None
         work = torch.empty(((n + 31) // 32 + 1) * (C + 4), dtype=torch.float32, device=dev) if any(need_p) else None
         if need_x or any(need_p):
-            L.check(L.get().mt_baseline_head_bwd(L.ptr(g), L.ptr(ctx.saved["pooled"]), L.ptr(ctx.saved["vc"]), n, hw, C, m, L.ptr(w1),
-                                                 L.ptr(b1), L.ptr(w2), L.ptr(dw1), L.ptr(db1), L.ptr(dw2), L.ptr(db2), L.ptr(dx), layout,
-                                                 L.ptr(work), L.stream_ptr()), "mt_baseline_head_bwd")
+            L.mt.baseline_head_bwd(g, ctx.saved["pooled"], ctx.saved["vc"], n, hw, C, m, w1, b1, w2, dw1, db1, dw2, db2, dx, layout, work)
         LAST_RUN.update(param_grads=any(need_p), dfeat=need_x)
         ctx.saved = None
         return None, None, dx, dw1, db1, dw2, db2

@@ -26,7 +26,6 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
     """keep_saved: the activation records belong to a launch plan (plans.py) and stay for its next replay; plan: the NetPlan whose
     backward phase is being recorded (it keeps the flat gradient buffer)."""
     lib = L.get()
-    st = L.stream_ptr()
     dev = dfeat.device
     N, H, W = shape
     blocks = model._blocks
@@ -80,15 +79,14 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
 
     def bn_finalize(bnctx, sums, gidx_gamma, d=None, z=None, rows=0):
         kabc = _new(dev, 3, bnctx.C)
-        L.check(lib.mt_bn_bwd_finalize(L.ptr(sums), slots, bnctx.count, L.ptr(P[gidx_gamma]), L.ptr(bnctx.mean_invstd), L.ptr(kabc),
-                                       L.ptr(grads[gidx_gamma]), L.ptr(grads[gidx_gamma + 1]), bnctx.C, tr, st), "mt_bn_bwd_finalize")
+        L.mt.bn_bwd_finalize(sums, slots, bnctx.count, P[gidx_gamma], bnctx.mean_invstd, kabc, grads[gidx_gamma], grads[gidx_gamma + 1],
+                             bnctx.C, tr)
         return kabc
 
     def act_bwd(din, z, bnctx, dout, rows, hw, act, gate=None, dpool=None, rowscale=None):
         sums = pool.take(bnctx.C)
-        L.check(lib.mt_bn_act_bwd(L.ptr(din), L.ptr(z), L.ptr(bnctx.scale), L.ptr(bnctx.shift), L.ptr(bnctx.mean_invstd), L.ptr(gate),
-                                  L.ptr(dpool), L.ptr(rowscale), L.ptr(dout), L.ptr(sums), slots, rows, bnctx.C, hw, act, st),
-                "mt_bn_act_bwd")
+        L.mt.bn_act_bwd(din, z, bnctx.scale, bnctx.shift, bnctx.mean_invstd, gate, dpool, rowscale, dout, sums, slots, rows, bnctx.C, hw,
+                        act)
         return sums
 
     def conv1x1_bwd(du, z, kabc, w, x_in, rows, cout, cin, gw_idx, need_dx_in, res=None, b_pro=None, pl=None):
@@ -98,7 +96,7 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
         forward kept its operand as planes, the weight-gradient GEMM."""
         if pl is not None:
             dz_p = L.planes_empty(rows, cout, dev)
-            L.check(lib.mt_bn_bwd_apply_planes(L.ptr(du), L.ptr(z), L.ptr(kabc), L.ptr(dz_p), rows, cout, st), "mt_bn_bwd_apply_planes")
+            L.mt.bn_bwd_apply_planes(du, z, kabc, dz_p, rows, cout)
             wdone = False
             if need[gw_idx] and pl.get("x_p") is not None:
                 run["wgrad_launches"] += 1
@@ -127,8 +125,7 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
             # over the widest tensors of the step; skinny_bwd.hip).  Runs on the main stream: it is the data gradient's critical path.
             run["wgrad_launches"] += 1
             dx_in = _new(dev, rows, cin)
-            L.check(lib.mt_conv1x1_bwd_fused(L.ptr(du), L.ptr(kabc), L.ptr(x_in), L.ptr(w), L.ptr(res), L.ptr(dx_in),
-                                             L.ptr(grads[gw_idx]), rows, cout, cin, st), "mt_conv1x1_bwd_fused")
+            L.mt.conv1x1_bwd_fused(du, kabc, x_in, w, res, dx_in, grads[gw_idx], rows, cout, cin)
             return dx_in
         if not need[gw_idx]:
             pass                                      # frozen weight: no launch
@@ -136,15 +133,13 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
             run["wgrad_launches"] += 1
             # few channels, very many rows: the result stays in MFMA accumulators while the rows stream (skinny_wgrad.hip)
             bp = b_pro if b_pro is not None else (None, None, None, 1)
-            side.launch(lambda: L.check(lib.mt_conv1x1_wgrad(L.ptr(du), L.ptr(z), L.ptr(kabc), L.ptr(x_in), L.ptr(bp[0]), L.ptr(bp[1]),
-                                                             L.ptr(bp[2]), bp[3], L.ptr(grads[gw_idx]), rows, cout, cin,
-                                                             L.stream_ptr()), "mt_conv1x1_wgrad"), reads=reads)
+            side.launch(lambda: L.mt.conv1x1_wgrad(du, z, kabc, x_in, bp[0], bp[1], bp[2], bp[3], grads[gw_idx], rows, cout, cin),
+                        reads=reads)
         elif not det and b_pro is not None and lib.mt_conv1x1_wgrad_wide_supported(cout, cin):
             run["wgrad_launches"] += 1
             # project convs of the late stages: 128-column slabs of the result, both operand transforms applied once (wide_wgrad.hip)
-            side.launch(lambda: L.check(lib.mt_conv1x1_wgrad_wide(L.ptr(du), L.ptr(z), L.ptr(kabc), L.ptr(x_in), L.ptr(b_pro[0]),
-                                                                  L.ptr(b_pro[1]), L.ptr(b_pro[2]), b_pro[3], L.ptr(grads[gw_idx]), rows,
-                                                                  cout, cin, L.stream_ptr()), "mt_conv1x1_wgrad_wide"), reads=reads)
+            side.launch(lambda: L.mt.conv1x1_wgrad_wide(du, z, kabc, x_in, b_pro[0], b_pro[1], b_pro[2], b_pro[3], grads[gw_idx], rows,
+                                                        cout, cin), reads=reads)
         else:
             run["wgrad_launches"] += 1
             side.launch(lambda: L.gemm(L.OP_TN, du, x_in, grads[gw_idx], cout, cin, rows, cout, cin, cin, prologue=L.PRO_BN_BWD,
@@ -155,8 +150,7 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
         dx_in = _new(dev, rows, cin)
         if rows >= STREAM_ROWS and lib.mt_conv1x1_rows_supported(cout, cin, 2):
             # data gradient as a streaming kernel: a = dz (BatchNorm backward folded on load), W used transposed
-            L.check(lib.mt_conv1x1_rows(L.ptr(du), L.ptr(z), L.ptr(w), cin, 1, L.ptr(kabc[0]), L.ptr(kabc[1]), L.ptr(kabc[2]), 1, 2,
-                                        L.ptr(res), L.ptr(dx_in), None, 1, rows, cout, cin, st), "mt_conv1x1_rows")
+            L.mt.conv1x1_rows(du, z, w, cin, 1, kabc[0], kabc[1], kabc[2], 1, 2, res, dx_in, None, 1, rows, cout, cin)
             return dx_in
         if res is not None:
             L.gemm(L.OP_NN, du, w, dx_in, rows, cin, cout, cout, cin, cin, prologue=L.PRO_BN_BWD, epilogue=L.EPI_BIAS_RES, A2=z,
@@ -200,10 +194,8 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
         se_scr = _new(dev, lib.mt_se_scratch_floats(N, s.cexp, s.cse))
         se = ix["se"]
         def se_part(parts, _da=None, _rec=rec, _bn=bn_d, _se=se, _s=s, _dg=dgate, _dp=dpre2, _dh=dhid, _dpo=dpooled, _hw=hw, _scr=se_scr):
-            L.check(lib.mt_se_bwd(L.ptr(_da), L.ptr(_rec["z_d"]), L.ptr(_bn.scale), L.ptr(_bn.shift), L.ptr(_rec["gate"]),
-                                  L.ptr(_rec["hidden"]), L.ptr(_rec["pooled"]), L.ptr(P[_se]), L.ptr(P[_se + 2]), L.ptr(_dg), L.ptr(_dp),
-                                  L.ptr(_dh), L.ptr(_dpo), L.ptr(grads[_se]), L.ptr(grads[_se + 1]), L.ptr(grads[_se + 2]),
-                                  L.ptr(grads[_se + 3]), N, _hw, _s.cexp, _s.cse, parts, L.ptr(_scr), L.stream_ptr()), "mt_se_bwd")
+            L.mt.se_bwd(_da, _rec["z_d"], _bn.scale, _bn.shift, _rec["gate"], _rec["hidden"], _rec["pooled"], P[_se], P[_se + 2], _dg, _dp,
+                        _dh, _dpo, grads[_se], grads[_se + 1], grads[_se + 2], grads[_se + 3], N, _hw, _s.cexp, _s.cse, parts, _scr)
         # early blocks (stages 0-2): two STREAMING passes that rebuild the project conv's data gradient from the narrow gradient
         # (skinny_se.hip): 3 instead of 6 passes over the expanded tensor, no da tensor.  (The same stage as mt_gemm epilogues measured
         # slower, profiles/r03_se_fused_epilogue_vs_streaming.txt; MT_EPI_SE_RED / MT_EPI_ACT_BWD remain mt_gemm epilogues, parity-tested
@@ -211,9 +203,8 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
         if not det and M_out >= STREAM_ROWS and lib.mt_se_stage_fused_supported(s.cout, s.cexp, hw):
             conv1x1_bwd(dsrc, rec["z_p"], kabc_p, P[ix["p"]], rec["z_d"], M_out, s.cout, s.cexp, ix["p"], False, b_pro=b_pro)   # weight gradient only
             def stage(mode, dg, g_, dpo, mi, out, st_):
-                L.check(lib.mt_se_stage_fused(L.ptr(dsrc), L.ptr(rec["z_p"]), L.ptr(kabc_p), L.ptr(P[ix["p"]]), L.ptr(rec["z_d"]),
-                                              L.ptr(bn_d.scale), L.ptr(bn_d.shift), mode, L.ptr(dg), L.ptr(g_), L.ptr(dpo), L.ptr(mi),
-                                              L.ptr(out), L.ptr(st_), slots, M_out, s.cout, s.cexp, hw, st), "mt_se_stage_fused")
+                L.mt.se_stage_fused(dsrc, rec["z_p"], kabc_p, P[ix["p"]], rec["z_d"], bn_d.scale, bn_d.shift, mode, dg, g_, dpo, mi, out,
+                                    st_, slots, M_out, s.cout, s.cexp, hw)
             L.zero_(dgate)
             stage(0, dgate, None, None, None, None, None)                       # (c+d) d gate
             se_part(4)                                                            # dgate -> dpooled
@@ -239,10 +230,8 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
         du_in = _new(dev, M_in, s.cexp)
         sums_in = pool.take(s.cexp)
         def dw_part(parts, _da=da, _rec=rec, _kabc=kabc_d, _bn=in_bn, _du_in=du_in, _sums=sums_in, _s=s, _ix=ix):
-            L.check(lib.mt_dwconv_bwd(L.ptr(_da), L.ptr(_rec["z_d"]), L.ptr(_kabc), L.ptr(P[_ix["d"]]), L.ptr(_rec["dw_in"]),
-                                      L.ptr(_bn.scale), L.ptr(_bn.shift), L.ptr(_bn.mean_invstd), L.ptr(_du_in), L.ptr(_sums), slots,
-                                      L.ptr(grads[_ix["d"]]), N, _s.hin, _s.hin, _s.cexp, _s.k, _s.s, parts, 1, None, None, L.stream_ptr()),
-                    "mt_dwconv_bwd")
+            L.mt.dwconv_bwd(_da, _rec["z_d"], _kabc, P[_ix["d"]], _rec["dw_in"], _bn.scale, _bn.shift, _bn.mean_invstd, _du_in, _sums,
+                            slots, grads[_ix["d"]], N, _s.hin, _s.hin, _s.cexp, _s.k, _s.s, parts, 1, None, None)
         # algorithmic HBM bytes of the pass: read da, z_d (M_out x cexp each) and the dw input's pre-activation (M_in x cexp: swish'
         # for the data gradient, swish for the weight gradient), write du_in (M_in x cexp)
         need_du_in = need_below[bi] or (s.has_expand and any(need[ix["e"]:ix["e"] + 3]))
@@ -280,13 +269,11 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
             run["stem_run"] = True
             if need[0]:
                 run["wgrad_launches"] += 1
-                L.check(lib.mt_stem_conv_wgrad(L.ptr(du_in), L.ptr(stem["z"]), L.ptr(kabc0), L.ptr(stem["x"]), 1 if stem["x"].dtype == torch.uint8 else 0, L.ptr(grads[0]), N, H, W, st),
-                        "mt_stem_conv_wgrad")
+                L.mt.stem_conv_wgrad(du_in, stem["z"], kabc0, stem["x"], 1 if stem["x"].dtype == torch.uint8 else 0, grads[0], N, H, W)
             if need_dx:
                 # the last operator of the walk: the transposed stem convolution, 32 -> 3 channels (csrc/stem_dgrad.hip)
                 dx = _new(dev, N, H, W, 3)
-                L.check(lib.mt_stem_conv_dgrad(L.ptr(du_in), L.ptr(stem["z"]), L.ptr(kabc0), L.ptr(P[0]), L.ptr(dx), N, H, W, st),
-                        "mt_stem_conv_dgrad")
+                L.mt.stem_conv_dgrad(du_in, stem["z"], kabc0, P[0], dx, N, H, W)
             dy = None
         del du_in
         if not keep_saved:

@@ -56,13 +56,12 @@ class _StatsPool:
         return v
 
 
-def _finalize(lib, bn_mod, ctx, count, training, gamma, beta, slots=SLOTS, st=None):
+def _finalize(bn_mod, ctx, count, training, gamma, beta, slots=SLOTS, st=None):
     """slots < 0 (deterministic mode): the producers' statistics are integer limbs (csrc/common.hpp stat_add, _StatsPool).
     st: the stream to launch on (default: the current stream)."""
     ctx.count = float(count)
-    L.check(lib.mt_bn_finalize(L.ptr(ctx.stats), slots, float(count), L.ptr(gamma), L.ptr(beta), L.ptr(bn_mod.running_mean),
-                               L.ptr(bn_mod.running_var), L.ptr(ctx.scale), L.ptr(ctx.shift), L.ptr(ctx.mean_invstd), ctx.C,
-                               bn_mod.eps, bn_mod.momentum, 1 if training else 0, L.stream_ptr() if st is None else st), "mt_bn_finalize")
+    L.mt.bn_finalize(ctx.stats, slots, float(count), gamma, beta, bn_mod.running_mean, bn_mod.running_var, ctx.scale, ctx.shift,
+                     ctx.mean_invstd, ctx.C, bn_mod.eps, bn_mod.momentum, 1 if training else 0, L.stream_ptr() if st is None else st)
     if training:
         _track(bn_mod.num_batches_tracked)
 
@@ -94,7 +93,6 @@ def weight_planes(model, params, exp, proj, head):
     """Plane tensors of the 1x1-conv weights that run on plane operands, re-split from the fp32 weights by ONE launch per forward
     (mt_split_planes_blk_multi; cf. tsf_planes.weight_planes).  Returns ({("e", block) | ("p", block) | "head": planes}, the saved
     serial of their holder or None)."""
-    lib = L.get()
     blocks = model._blocks
     sel, pos = [], 3
     for bi, blk in enumerate(blocks):
@@ -129,8 +127,7 @@ def weight_planes(model, params, exp, proj, head):
         host = torch.tensor(rows, dtype=torch.int64).pin_memory()
         cache = caches[ident] = dict(holder=holder, host=host, table=host.to(dev, non_blocking=True), blocks=first, count=len(rows),
                                      serial=plans.PlaneSerial("the 1x1-conv weights"))
-    L.check(lib.mt_split_planes_blk_multi(L.ptr(cache["table"]), cache["count"], cache["blocks"], L.stream_ptr()),
-            "mt_split_planes_blk_multi")       # (L.ptr: a plan being recorded pins the table)
+    L.mt.split_planes_blk_multi(cache["table"], cache["count"], cache["blocks"])       # (a plan being recorded pins the table)
     return cache["holder"], cache["serial"].touch([w for _, w, _, _ in sel])
 
 
@@ -169,7 +166,6 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
     """x_nhwc [N,H,W,3] contiguous fp32.  Returns (feat [N*Ho*Wo, 1280], saved or None, block outputs or None).
     plan: the plans.NetPlan being recorded (it keeps the gate buffer and the tracked counters for its replays)."""
     lib = L.get()
-    st = L.stream_ptr()
     dev = x_nhwc.device
     N, H, W, _ = x_nhwc.shape
     blocks = model._blocks
@@ -180,7 +176,6 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
     it = iter(params)
     slots = -SLOTS if det else SLOTS
     epi = L.EPI_STATS if training else L.EPI_STORE
-    sptr = (lambda b_: L.ptr(b_.stats)) if training else (lambda b_: None)
     saved = {"blocks": []} if save else None
     pl_exp, pl_proj, pl_head = planes_scope(model, N)
     wpl, w_serial = weight_planes(model, params, pl_exp, pl_proj, pl_head)
@@ -194,14 +189,13 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
     # stem: streaming MFMA kernel (stem_fwd.hip; uint8 crops converted on the fly, BatchNorm statistics in the same pass).  The
     # im2col-prologue GEMM it replaced (K = 27 taps padded to 28) stays the path for crops wider than the kernel's LDS row tile.
     if W <= 512 and H == W:
-        L.check(lib.mt_stem_conv_fwd(L.ptr(x_nhwc), 1 if x_nhwc.dtype == torch.uint8 else 0, L.ptr(w_stem), L.ptr(z),
-                                     sptr(bn), slots, N, H, W, st), "mt_stem_conv_fwd")
+        L.mt.stem_conv_fwd(x_nhwc, 1 if x_nhwc.dtype == torch.uint8 else 0, w_stem, z, bn.stats, slots, N, H, W)
     else:
         wp = _new(dev, arch.STEM_COUT, 28)
-        L.check(lib.mt_conv_weight_pack(L.ptr(w_stem), L.ptr(wp), arch.STEM_COUT, 3, 3, 28, 0, st), "mt_conv_weight_pack")
+        L.mt.conv_weight_pack(w_stem, wp, arch.STEM_COUT, 3, 3, 28, 0)
         L.gemm(L.OP_NT, x_nhwc, wp, z, N * Hc * Wc, arch.STEM_COUT, 28, 28, 28, arch.STEM_COUT, prologue=L.PRO_IM2COL, epilogue=epi,
                stats=bn.stats, stats_slots=slots, conv=(H, W, 3, Hc, Wc, 3, 2, 0, 0, 1 if x_nhwc.dtype == torch.uint8 else 0))
-    _finalize(lib, model._bn0, bn, N * Hc * Wc, training, g0, b0, slots, st)
+    _finalize(model._bn0, bn, N * Hc * Wc, training, g0, b0, slots)
     if save:
         saved["stem"] = dict(x=x_nhwc, z=z, bn=bn)
     cur_z, cur_bn = z, bn        # "virtual" activated tensor: swish(bn(z))
@@ -227,11 +221,10 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
                               stats_slots=slots)
                 rec.update(y_p=y_p, we_p=wpl[("e", bi)])
             elif M_in >= STREAM_ROWS and lib.mt_conv1x1_rows_supported(s.cin, s.cexp, 0):   # few channels, very many rows: streaming kernel
-                L.check(lib.mt_conv1x1_rows(L.ptr(y), None, L.ptr(w_e), s.cin, 0, None, None, None, 1, 0, None, L.ptr(z_e),
-                                            sptr(bn_e), slots, M_in, s.cin, s.cexp, st), "mt_conv1x1_rows")
+                L.mt.conv1x1_rows(y, None, w_e, s.cin, 0, None, None, None, 1, 0, None, z_e, bn_e.stats, slots, M_in, s.cin, s.cexp)
             else:
                 L.gemm(L.OP_NT, y, w_e, z_e, M_in, s.cexp, s.cin, s.cin, s.cin, s.cexp, epilogue=epi, stats=bn_e.stats, stats_slots=slots)
-            _finalize(lib, blk._bn0, bn_e, M_in, training, g, b, slots, st)
+            _finalize(blk._bn0, bn_e, M_in, training, g, b, slots)
             rec.update(z_e=z_e, bn_e=bn_e)
             dw_in, dw_bn = z_e, bn_e
         else:
@@ -239,49 +232,43 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
         w_d, g, b = next(it), next(it), next(it)
         bn_d = _BNCtx(dev, s.cexp, training, pool)
         z_d = _new(dev, M_out, s.cexp)
-        L.check(lib.mt_dwconv_fwd(L.ptr(dw_in), L.ptr(dw_bn.scale), L.ptr(dw_bn.shift), L.ptr(w_d), L.ptr(z_d), sptr(bn_d),
-                                  slots, N, s.hin, s.hin, s.cexp, s.k, s.s, 1, st), "mt_dwconv_fwd")
-        _finalize(lib, blk._bn1, bn_d, M_out, training, g, b, slots, st)
+        L.mt.dwconv_fwd(dw_in, dw_bn.scale, dw_bn.shift, w_d, z_d, bn_d.stats, slots, N, s.hin, s.hin, s.cexp, s.k, s.s, 1)
+        _finalize(blk._bn1, bn_d, M_out, training, g, b, slots)
         w_r, b_r, w_x, b_x = next(it), next(it), next(it), next(it)
         pooled, gate = _new(dev, N, s.cexp), _new(dev, N, s.cexp)
         hidden = _new(dev, N, s.cse)          # squeeze pre-activations: the gate kernel reads them (and backward keeps them)
         hw = s.hout * s.hout
         parts = lib.mt_se_pool_parts(N, hw, s.cexp)
         partial = _new(dev, N, parts, s.cexp)
-        L.check(lib.mt_se_pool_fwd(L.ptr(z_d), L.ptr(bn_d.scale), L.ptr(bn_d.shift), L.ptr(partial), N, hw, s.cexp, parts, st),
-                "mt_se_pool_fwd")
-        L.check(lib.mt_se_gate_fwd(L.ptr(partial), parts, L.ptr(w_r), L.ptr(b_r), L.ptr(w_x), L.ptr(b_x), L.ptr(pooled), L.ptr(gate),
-                                   L.ptr(hidden), N, s.cexp, s.cse, st), "mt_se_gate_fwd")
+        L.mt.se_pool_fwd(z_d, bn_d.scale, bn_d.shift, partial, N, hw, s.cexp, parts)
+        L.mt.se_gate_fwd(partial, parts, w_r, b_r, w_x, b_x, pooled, gate, hidden, N, s.cexp, s.cse)
         w_p, g, b = next(it), next(it), next(it)
         bn_p = _BNCtx(dev, s.cout, training, pool)
         z_p = _new(dev, M_out, s.cout)
         if pl_proj[bi]:
             # 7 x 7 stage: the operand swish(bn1(z_d)) * gate written once as planes (kept for the weight gradient), the GEMM only DMAs
             a_p = L.planes_empty(M_out, s.cexp, dev)
-            L.check(lib.mt_bn_swish_gate_planes(L.ptr(z_d), L.ptr(bn_d.scale), L.ptr(bn_d.shift), L.ptr(gate), hw, L.ptr(a_p), M_out,
-                                                s.cexp, st), "mt_bn_swish_gate_planes")
+            L.mt.bn_swish_gate_planes(z_d, bn_d.scale, bn_d.shift, gate, hw, a_p, M_out, s.cexp)
             L.gemm_planes(L.OP_NT, a_p, wpl[("p", bi)], M_out, s.cout, s.cexp, Cout=z_p, ldc=s.cout, epilogue=epi, stats=bn_p.stats,
                           stats_slots=slots)
             rec.update(a_p=a_p, wp_p=wpl[("p", bi)])
         elif M_out >= STREAM_ROWS and lib.mt_conv1x1_rows_supported(s.cexp, s.cout, 1):
-            L.check(lib.mt_conv1x1_rows(L.ptr(z_d), None, L.ptr(w_p), s.cexp, 0, L.ptr(bn_d.scale), L.ptr(bn_d.shift), L.ptr(gate), hw, 1,
-                                        None, L.ptr(z_p), sptr(bn_p), slots, M_out, s.cexp, s.cout, st), "mt_conv1x1_rows")
+            L.mt.conv1x1_rows(z_d, None, w_p, s.cexp, 0, bn_d.scale, bn_d.shift, gate, hw, 1, None, z_p, bn_p.stats, slots, M_out, s.cexp,
+                              s.cout)
         else:
             L.gemm(L.OP_NT, z_d, w_p, z_p, M_out, s.cout, s.cexp, s.cexp, s.cexp, s.cout, prologue=L.PRO_BN_SWISH_GATE, epilogue=epi,
                    scale=bn_d.scale, shift=bn_d.shift, gate=gate, hw=hw, stats=bn_p.stats, stats_slots=slots)
-        _finalize(lib, blk._bn2, bn_p, M_out, training, g, b, slots, st)
+        _finalize(blk._bn2, bn_p, M_out, training, g, b, slots)
         # block output: bn2(z_p) [* drop-connect gate] [+ block input]
         dc = dc_gates.get(bi)
         y_new = _new(dev, M_out, s.cout)
         next_planes = pl_exp[bi + 1] if bi + 1 < len(blocks) else pl_head
         if next_planes:
             y_p = L.planes_empty(M_out, s.cout, dev)
-            L.check(lib.mt_bn_act_fwd_planes(L.ptr(z_p), L.ptr(bn_p.scale), L.ptr(bn_p.shift), L.ptr(y if s.skip else None), L.ptr(y_new),
-                                             M_out, s.cout, 0, L.ptr(dc), hw, L.ptr(y_p), st), "mt_bn_act_fwd_planes")
+            L.mt.bn_act_fwd_planes(z_p, bn_p.scale, bn_p.shift, y if s.skip else None, y_new, M_out, s.cout, 0, dc, hw, y_p)
         else:
             y_p = None
-            L.check(lib.mt_bn_act_fwd(L.ptr(z_p), L.ptr(bn_p.scale), L.ptr(bn_p.shift), L.ptr(y if s.skip else None), L.ptr(y_new),
-                                      M_out, s.cout, 0, L.ptr(dc), hw, st), "mt_bn_act_fwd")
+            L.mt.bn_act_fwd(z_p, bn_p.scale, bn_p.shift, y if s.skip else None, y_new, M_out, s.cout, 0, dc, hw)
         if save:
             rec.update(y_in=y, dw_in=dw_in, dw_bn=dw_bn, z_d=z_d, bn_d=bn_d, pooled=pooled, hidden=hidden, gate=gate, z_p=z_p,
                        bn_p=bn_p, dc=dc)
@@ -302,10 +289,9 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
     else:
         L.gemm(L.OP_NT, y, w_h, z_h, M, arch.HEAD_COUT, arch.HEAD_CIN, arch.HEAD_CIN, arch.HEAD_CIN, arch.HEAD_COUT, epilogue=epi,
                stats=bn_h.stats, stats_slots=slots)
-    _finalize(lib, model._bn1, bn_h, M, training, g, b, slots, st)
+    _finalize(model._bn1, bn_h, M, training, g, b, slots)
     feat = _new(dev, M, arch.HEAD_COUT)
-    L.check(lib.mt_bn_act_fwd(L.ptr(z_h), L.ptr(bn_h.scale), L.ptr(bn_h.shift), None, L.ptr(feat), M, arch.HEAD_COUT, 1, None, 1,
-                              st), "mt_bn_act_fwd")
+    L.mt.bn_act_fwd(z_h, bn_h.scale, bn_h.shift, None, feat, M, arch.HEAD_COUT, 1, None, 1)
     if save:
         saved["head"] = dict(y_in=y, z=z_h, bn=bn_h, y_p=y_p if pl_head else None, w_p=wpl.get("head"))
         saved["w_serial"] = w_serial

@@ -295,19 +295,18 @@ class Engine:
         overwritten by the next call with the same T)."""
         check_side(H, W)
         dev = src.device
-        lib, st = L.get(), L.stream_ptr()
+        st = L.stream_ptr()
         self.weights()
         out = self.out_rows(dev, T)
         es = src.element_size()
         for t0 in range(0, T, self.chunk):
             n = min(self.chunk, T - t0)
             prog = self.program(dev, n, H, W)
-            L.check(lib.mt_face_ingest(src.data_ptr() + t0 * strides[0] * es, int(is_u8), strides[0], strides[1], strides[2], strides[3],
-                                       n, H, W, int(standardize), prog["in4"], st), "mt_face_ingest")
+            L.mt.face_ingest(src.data_ptr() + t0 * strides[0] * es, int(is_u8), strides[0], strides[1], strides[2], strides[3], n, H, W,
+                             int(standardize), prog["in4"], st)
             for fn, args in prog["calls"]:
                 rc = fn(*args, st)
                 if rc:
                     L.check(rc, fn.__name__)
-            L.check(lib.mt_l2_normalize_rows(prog["lin"], 512, out.data_ptr() + t0 * 512 * 4, 512, n, 512, NORM_EPS, st),
-                    "mt_l2_normalize_rows")
+            L.mt.l2_normalize_rows(prog["lin"], 512, out[t0:], 512, n, 512, NORM_EPS, st)
         return out

@@ -270,8 +270,7 @@ def aggregate_attentions(attentions, heads, num_frames, frames_per_identity, sca
     space, time_ = attentions
     bh, _, n = space.shape
     out = torch.empty(3, num_frames, dtype=torch.float32, device=space.device)
-    L.check(L.get().mt_attn_aggregate(L.ptr(space.contiguous()), L.ptr(time_.contiguous()), L.ptr(out), bh, n, num_frames,
-                                      float(scale_factor), L.stream_ptr()), "mt_attn_aggregate")
+    L.mt.attn_aggregate(space.contiguous(), time_.contiguous(), out, bh, n, num_frames, float(scale_factor))
     agg = out.cpu().tolist()
     comb = agg[-1]
     identity = []

@@ -166,13 +166,11 @@ class ClusterPlan:
         """embeddings [T, dim] fp32 on the device, rows in video order -> IdentityClusters (views of this plan's buffers)."""
         _check_embeddings(embeddings, self.counts, self.dim)
         e = embeddings.detach().contiguous()
-        lib, V, T = L.get(), len(self.counts), sum(self.counts)
-        L.check(lib.mt_identity_adjacency(L.ptr(e), L.ptr(self._offsets_dev), L.ptr(self._prefix_dev), V, T, self.dim, self.total_tiles,
-                                          self.max_faces, float(similarity_threshold), L.ptr(self.adjacency), L.ptr(self.err_flag),
-                                          L.stream_ptr()), "mt_identity_adjacency")
-        L.check(lib.mt_identity_components(L.ptr(self.adjacency), L.ptr(self._offsets_dev), None, V, T, self.max_faces, L.ptr(self.labels),
-                                           L.ptr(self.n_identities), L.ptr(self.sizes), L.ptr(self.err_flag), L.stream_ptr()),
-                "mt_identity_components")
+        V, T = len(self.counts), sum(self.counts)
+        L.mt.identity_adjacency(e, self._offsets_dev, self._prefix_dev, V, T, self.dim, self.total_tiles, self.max_faces,
+                                float(similarity_threshold), self.adjacency, self.err_flag)
+        L.mt.identity_components(self.adjacency, self._offsets_dev, None, V, T, self.max_faces, self.labels, self.n_identities, self.sizes,
+                                 self.err_flag)
         return IdentityClusters(self.labels, self.n_identities, self.sizes, self.offsets, self.err_flag)
 
 
@@ -202,11 +200,8 @@ def cluster_similarities(similarities, similarity_threshold=0.80):
     source = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
     n_identities = torch.empty(1, dtype=torch.int32, device=dev)
     err = L.zeros(1, torch.int32, dev)
-    lib = L.get()
-    L.check(lib.mt_identity_adjacency_sim(L.ptr(s), n, float(similarity_threshold), L.ptr(adj), L.ptr(source), L.stream_ptr()),
-            "mt_identity_adjacency_sim")
-    L.check(lib.mt_identity_components(L.ptr(adj), L.ptr(offsets), L.ptr(source), 1, n, max(n, 1), L.ptr(labels), L.ptr(n_identities), L.ptr(sizes),
-                                       L.ptr(err), L.stream_ptr()), "mt_identity_components")
+    L.mt.identity_adjacency_sim(s, n, float(similarity_threshold), adj, source)
+    L.mt.identity_components(adj, offsets, source, 1, n, max(n, 1), labels, n_identities, sizes, err)
     out = IdentityClusters(labels, n_identities, sizes, [0, n], err)
     out.adjacency = adj
     return out

@@ -70,9 +70,8 @@ class EpochMetrics:
         mc = None if multiclass_labels is None else multiclass_labels.detach().reshape(-1).to(torch.float32).contiguous()
         if self.store_scores.numel() != self.capacity or self.store_labels.numel() != self.capacity:
             raise ValueError("EpochMetrics.update: the sample store does not hold `capacity` elements")
-        L.check(L.get().mt_metrics_update(L.ptr(x), L.ptr(y), L.ptr(lo), L.ptr(mc), L.ptr(self._ints), L.ptr(self._loss),
-                                          self._ints[_SLOTS:].data_ptr(), L.ptr(self.store_scores), L.ptr(self.store_labels),
-                                          self.capacity, n, L.stream_ptr()), "mt_metrics_update")
+        L.mt.metrics_update(x, y, lo, mc, self._ints, self._loss, self._ints[_SLOTS:], self.store_scores, self.store_labels,
+                            self.capacity, n)
 
     def auc_counts(self, n=None):
         """(gt, eq, n_pos, n_neg) of the first n stored samples (default: all of them), as Python ints: the number of (positive,
@@ -83,8 +82,7 @@ class EpochMetrics:
         blocks = (n + AUC_BLOCK - 1) // AUC_BLOCK
         partials = torch.empty(max(4 * blocks, 1), dtype=torch.int64, device=self.device)
         out = torch.empty(4, dtype=torch.int64, device=self.device)
-        L.check(L.get().mt_metrics_auc(L.ptr(self.store_scores), L.ptr(self.store_labels), n, L.ptr(partials), L.ptr(out),
-                                       L.stream_ptr()), "mt_metrics_auc")
+        L.mt.metrics_auc(self.store_scores, self.store_labels, n, partials, out)
         return tuple(out.cpu().tolist())
 
     def compute(self):

@@ -52,7 +52,6 @@ class FusedSGD(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = L.get()
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -62,8 +61,7 @@ class FusedSGD(torch.optim.Optimizer):
                     raise L.MintimeHipError("FusedSGD needs contiguous fp32 parameters and gradients")
                 L.ptr(p)                                   # refuses CPU tensors: there is no CPU path
             table, blocks = self._table(gi, ps)
-            L.check(lib.mt_sgd_multi(table.data_ptr(), len(ps), blocks, float(group["lr"]), float(group["weight_decay"]),
-                                     L.stream_ptr()), "mt_sgd_multi")
+            L.mt.sgd_multi(table, len(ps), blocks, float(group["lr"]), float(group["weight_decay"]))
         _weights_changed()
         return loss
 
@@ -106,7 +104,6 @@ class _FusedAdamBase(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = L.get()
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -138,9 +135,8 @@ class _FusedAdamBase(torch.optim.Optimizer):
                 step_size = group["lr"] / (1.0 - b1 ** t)
                 bc2_sqrt = (1.0 - b2 ** t) ** 0.5
                 table, blocks = self._table((gi, t0 if len(by_step) > 1 else -1), members)
-                L.check(lib.mt_adam_multi(table.data_ptr(), len(members), blocks, float(group["lr"]), float(group["weight_decay"]),
-                                          float(b1), float(b2), float(group["eps"]), float(step_size), float(bc2_sqrt),
-                                          1 if self._decoupled else 0, L.stream_ptr()), "mt_adam_multi")
+                L.mt.adam_multi(table, len(members), blocks, float(group["lr"]), float(group["weight_decay"]), float(b1),
+                                float(b2), float(group["eps"]), float(step_size), float(bc2_sqrt), 1 if self._decoupled else 0)
         _weights_changed()
         return loss
 
@@ -164,8 +160,7 @@ class _BCEWithLogits(torch.autograd.Function):
             raise ValueError("logits and labels must have the same number of elements")
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dx = torch.empty_like(x)
-        L.check(L.get().mt_bce_logits(L.ptr(x), L.ptr(y), float(pos_weight), L.ptr(loss), L.ptr(dx), x.numel(), L.stream_ptr()),
-                "mt_bce_logits")
+        L.mt.bce_logits(x, y, float(pos_weight), loss, dx, x.numel())
         ctx.save_for_backward(dx)
         ctx.shape = logits.shape
         return loss.reshape(())

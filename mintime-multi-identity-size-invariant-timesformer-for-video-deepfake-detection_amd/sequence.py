@@ -150,9 +150,8 @@ def build_batch(plans: Sequence[ClipPlan], num_frames: int, num_patches: int = 4
     ident = torch.empty(B, F, F, dtype=torch.bool, device=dev)
     sizes = torch.empty(B, F, dtype=torch.int32, device=dev)
     positions = torch.empty(B, 1 + F * num_patches, dtype=torch.int64, device=dev)
-    L.check(L.get().mt_build_clip_inputs(L.ptr(d[o[0]:]), L.ptr(d[o[1]:]), L.ptr(d[o[2]:]), L.ptr(d[o[3]:]), L.ptr(mask), L.ptr(ident),
-                                         L.ptr(sizes), L.ptr(positions), B, F, num_patches, MAX_IDENTITIES,
-                                         1 if modes.pop() == "predict" else 0, L.stream_ptr()), "mt_build_clip_inputs")
+    L.mt.build_clip_inputs(d[o[0]:], d[o[1]:], d[o[2]:], d[o[3]:], mask, ident, sizes, positions, B, F, num_patches, MAX_IDENTITIES,
+                           1 if modes.pop() == "predict" else 0)
     out = dict(mask=mask, identities_mask=ident, positions=positions, size_embedding_dev=sizes)
     out["size_embedding"] = sizes.cpu() if size_embedding_on_host else sizes
     return out

@@ -231,8 +231,7 @@ def ingest(src, fidx, normalize, layout, split=None):
     out = torch.empty(B, split, H, W, 4, dtype=torch.float32, device=src.device)
     out2 = torch.empty(B, n - split, H, W, 4, dtype=torch.float32, device=src.device) if split < n else None
     idx = torch.tensor(fidx, dtype=torch.int32).to(src.device)
-    L.check(L.get().mt_sf_ingest(L.ptr(src), int(is_u8), sb, sf, sh, sw, sc, L.ptr(idx), n, split, B, H, W, int(normalize), L.ptr(out),
-                                 L.ptr(out2), L.stream_ptr()), "mt_sf_ingest")
+    L.mt.sf_ingest(src, int(is_u8), sb, sf, sh, sw, sc, idx, n, split, B, H, W, int(normalize), out, out2)
     return out if out2 is None else (out, out2)
 
 
@@ -274,8 +273,7 @@ def ingest_bwd(dout, dout2, fidx, shape, normalize, layout, split=None):
     dsrc = torch.empty(tuple(shape), dtype=torch.float32, device=dout.device)
     st, jl = _sources_on_device(tuple(fidx), F, dout.device)
     sb, sf, sh, sw, sc = _src_strides(dsrc, layout)
-    L.check(L.get().mt_sf_ingest_bwd(L.ptr(dout), L.ptr(dout2), L.ptr(st), L.ptr(jl), F, n, split, B, H, W, int(normalize), L.ptr(dsrc),
-                                     sb, sf, sh, sw, sc, L.stream_ptr()), "mt_sf_ingest_bwd")
+    L.mt.sf_ingest_bwd(dout, dout2, st, jl, F, n, split, B, H, W, int(normalize), dsrc, sb, sf, sh, sw, sc)
     return dsrc
 
 
@@ -406,9 +404,8 @@ def ingest_resize(src, fidx, normalize, layout, geom, split=None):
     out2 = torch.empty(B, n - split, Ho, Wo, 4, dtype=torch.float32, device=src.device) if split < n else None
     idx = torch.tensor(fidx, dtype=torch.int32).to(src.device)
     t = _resize_tables(H, W, geom, src.device)
-    L.check(L.get().mt_sf_ingest_resize(L.ptr(src), int(is_u8), sb, sf, sh, sw, sc, L.ptr(idx), n, split, B, H, W, L.ptr(t[0]), L.ptr(t[1]),
-                                        L.ptr(t[5]), L.ptr(t[6]), Hr, Wr, top, left, Ho, Wo, int(normalize), L.ptr(out), L.ptr(out2),
-                                        L.stream_ptr()), "mt_sf_ingest_resize")
+    L.mt.sf_ingest_resize(src, int(is_u8), sb, sf, sh, sw, sc, idx, n, split, B, H, W, t[0], t[1], t[5], t[6], Hr, Wr, top, left, Ho, Wo,
+                          int(normalize), out, out2)
     return out if out2 is None else (out, out2)
 
 
@@ -439,9 +436,8 @@ def ingest_resize_bwd(dout, dout2, fidx, shape, normalize, layout, geom, split=N
     st, jl = _sources_on_device(tuple(fidx), F, dout.device)
     t = _resize_tables(H, W, geom, dout.device)
     sb, sf, sh, sw, sc = _src_strides(dsrc, layout)
-    L.check(L.get().mt_sf_ingest_resize_bwd(L.ptr(dout), L.ptr(dout2), L.ptr(st), L.ptr(jl), F, n, split, B, H, W, L.ptr(t[2]), L.ptr(t[3]),
-                                            L.ptr(t[4]), L.ptr(t[7]), L.ptr(t[8]), L.ptr(t[9]), Hr, Wr, top, left, Ho, Wo, int(normalize),
-                                            L.ptr(dsrc), sb, sf, sh, sw, sc, L.stream_ptr()), "mt_sf_ingest_resize_bwd")
+    L.mt.sf_ingest_resize_bwd(dout, dout2, st, jl, F, n, split, B, H, W, t[2], t[3], t[4], t[7], t[8], t[9], Hr, Wr, top, left, Ho, Wo,
+                              int(normalize), dsrc, sb, sf, sh, sw, sc)
     return dsrc
 
 

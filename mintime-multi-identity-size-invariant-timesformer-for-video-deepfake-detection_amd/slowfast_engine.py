@@ -77,8 +77,7 @@ def conv_fwd(x, w, conv, pro, out=None, stats=True):
         part = torch.empty(int(lib.mt_conv3d_part_floats(C.byref(d))), dtype=torch.float32, device=out.device)
         st = torch.empty(2 * cout, dtype=torch.float64, device=out.device)
     sc, sh = pro if pro is not None else (None, None)
-    L.check(lib.mt_conv3d_fwd(C.byref(d), L.ptr(x.t), L.ptr(sc), L.ptr(sh), L.ptr(wp), L.ptr(out), 0, L.ptr(part), L.ptr(st),
-                              L.stream_ptr()), "mt_conv3d_fwd")
+    L.mt.conv3d_fwd(d, x.t, sc, sh, wp, out, 0, part, st)
     return Fm(out, x.N, To, Ho, Wo), st
 
 
@@ -91,8 +90,7 @@ def conv_wgrad(x, pro, dz, w, conv):
     dwp = torch.empty(w.shape[0], kd, dtype=torch.float32, device=dz.t.device)
     ws = torch.empty(splits * w.shape[0] * kd, dtype=torch.float32, device=dz.t.device) if splits > 1 else None
     sc, sh = pro if pro is not None else (None, None)
-    L.check(lib.mt_conv3d_wgrad(C.byref(d), L.ptr(x.t), L.ptr(sc), L.ptr(sh), L.ptr(dz.t), L.ptr(dwp), L.ptr(ws), splits, L.stream_ptr()),
-            "mt_conv3d_wgrad")
+    L.mt.conv3d_wgrad(d, x.t, sc, sh, dz.t, dwp, ws, splits)
     kt, kh, kw = conv.k
     g = dwp.reshape(w.shape[0], kt, kh, kw, x.C)[..., :w.shape[1]]
     return g.permute(0, 4, 1, 2, 3).contiguous()
@@ -101,8 +99,7 @@ def conv_wgrad(x, pro, dz, w, conv):
 def conv_dgrad(x, dz, w, conv, out, accumulate):
     """out (+)= d conv / d pro(x) applied to dz; out is a [rows_x, C] tensor (any pitch)."""
     d, _ = _desc(Fm(out, x.N, x.T, x.H, x.W), conv.k, conv.s, conv.p, w.shape[0], dz.ld)
-    L.check(L.get().mt_conv3d_dgrad(C.byref(d), L.ptr(dz.t), L.ptr(_pack_wt(w)), L.ptr(out), int(accumulate), L.stream_ptr()),
-            "mt_conv3d_dgrad")
+    L.mt.conv3d_dgrad(d, dz.t, _pack_wt(w), out, int(accumulate))
 
 
 def _pack_w_stem_dgrad(w):
@@ -115,8 +112,7 @@ def _pack_w_stem_dgrad(w):
 def stem_dgrad(x, dz, w):
     """The stem's data gradient down to the packed clip: dz = dL/dz of the stem convolution of x -> dL/dx as [N, T, H, W, 4]."""
     dx = torch.empty(x.N, x.T, x.H, x.W, 4, dtype=torch.float32, device=dz.t.device)
-    L.check(L.get().mt_sf_stem_dgrad(L.ptr(dz.t), dz.ld, L.ptr(_pack_w_stem_dgrad(w)), L.ptr(dx), x.N, x.T, x.H, x.W, w.shape[2],
-                                     w.shape[0], L.stream_ptr()), "mt_sf_stem_dgrad")
+    L.mt.sf_stem_dgrad(dz.t, dz.ld, _pack_w_stem_dgrad(w), dx, x.N, x.T, x.H, x.W, w.shape[2], w.shape[0])
     return dx
 
 
@@ -137,9 +133,8 @@ def bn_fwd(ctx, key, stats, count):
     b.mi = torch.empty(2 * Cn, dtype=torch.float32, device=dev)
     if ctx.training and mod.momentum is None:
         raise NotImplementedError("SlowFast: BatchNorm momentum None (cumulative average) is not supported")
-    L.check(L.get().mt_bn_finalize(L.ptr(stats) if ctx.training else None, 1, float(count), L.ptr(gamma), L.ptr(beta),
-                                   L.ptr(mod.running_mean), L.ptr(mod.running_var), L.ptr(b.scale), L.ptr(b.shift), L.ptr(b.mi), Cn,
-                                   float(mod.eps), float(mod.momentum or 0.0), int(ctx.training), L.stream_ptr()), "mt_bn_finalize")
+    L.mt.bn_finalize(stats if ctx.training else None, 1, float(count), gamma, beta, mod.running_mean, mod.running_var, b.scale, b.shift,
+                     b.mi, Cn, float(mod.eps), float(mod.momentum or 0.0), int(ctx.training))
     if ctx.training and mod.num_batches_tracked is not None:
         mod.num_batches_tracked.add_(1)
     return b
@@ -155,16 +150,13 @@ def bn_bwd(ctx, b, g, z, relu_bn=None, mask=None, out=None, accumulate=False):
     mt, ldm = (mask.t, mask.ld) if mask is not None else (None, 0)
     part = torch.empty(int(lib.mt_sf_bn_bwd_part_floats(rows, Cn)), dtype=torch.float32, device=dev)
     st = torch.empty(2 * Cn, dtype=torch.float64, device=dev)
-    L.check(lib.mt_sf_bn_relu_bwd_stats(L.ptr(g.t), g.ld, L.ptr(z.t), z.ld, L.ptr(sc), L.ptr(sh), L.ptr(mt), ldm, L.ptr(b.mi), L.ptr(part),
-                                        L.ptr(st), rows, Cn, L.stream_ptr()), "mt_sf_bn_relu_bwd_stats")
+    L.mt.sf_bn_relu_bwd_stats(g.t, g.ld, z.t, z.ld, sc, sh, mt, ldm, b.mi, part, st, rows, Cn)
     kabc = torch.empty(3 * Cn, dtype=torch.float32, device=dev)
     dgamma, dbeta = ctx.grad_buf(b.key + ".weight"), ctx.grad_buf(b.key + ".bias")
-    L.check(lib.mt_bn_bwd_finalize(L.ptr(st), 1, float(b.count), L.ptr(ctx.P[b.key + ".weight"]), L.ptr(b.mi), L.ptr(kabc), L.ptr(dgamma),
-                                   L.ptr(dbeta), Cn, int(b.training), L.stream_ptr()), "mt_bn_bwd_finalize")
+    L.mt.bn_bwd_finalize(st, 1, float(b.count), ctx.P[b.key + ".weight"], b.mi, kabc, dgamma, dbeta, Cn, int(b.training))
     if out is None:
         out = torch.empty(rows, Cn, dtype=torch.float32, device=dev)
-    L.check(lib.mt_sf_bn_relu_bwd_apply(L.ptr(g.t), g.ld, L.ptr(z.t), z.ld, L.ptr(sc), L.ptr(sh), L.ptr(mt), ldm, L.ptr(kabc), L.ptr(out),
-                                        out.stride(0), int(accumulate), rows, Cn, L.stream_ptr()), "mt_sf_bn_relu_bwd_apply")
+    L.mt.sf_bn_relu_bwd_apply(g.t, g.ld, z.t, z.ld, sc, sh, mt, ldm, kabc, out, out.stride(0), int(accumulate), rows, Cn)
     return Fm(out, z.N, z.T, z.H, z.W)
 
 
@@ -205,8 +197,7 @@ def block_fwd(ctx, prefix, x, pro, kt, stride, first, out=None):
         res, ldr, rsc, rsh = x.t, x.ld, None, None
     if out is None:
         out = torch.empty(zc.rows, zc.C, dtype=torch.float32, device=zc.t.device)
-    L.check(L.get().mt_sf_bn_relu_fwd(L.ptr(zc.t), zc.ld, L.ptr(bc.scale), L.ptr(bc.shift), L.ptr(res), ldr, L.ptr(rsc), L.ptr(rsh),
-                                      L.ptr(out), out.stride(0), zc.rows, zc.C, L.stream_ptr()), "mt_sf_bn_relu_fwd")
+    L.mt.sf_bn_relu_fwd(zc.t, zc.ld, bc.scale, bc.shift, res, ldr, rsc, rsh, out, out.stride(0), zc.rows, zc.C)
     y = Fm(out, zc.N, zc.T, zc.H, zc.W)
     r.x, r.pro, r.za, r.zb, r.zc, r.ba, r.bb, r.bc, r.ca, r.cb, r.cc, r.y = x, pro, za, zb, zc, ba, bb, bc, ca, cb, cc, y
     return y, r
@@ -223,8 +214,7 @@ def block_bwd(ctx, r, gy):
         ctx.add_wgrad(r.c1.key, r.x, r.pro, dz1, r.c1)
         conv_dgrad(r.x, dz1, P[r.c1.key + ".weight"], r.c1, gx, False)
     else:
-        L.check(L.get().mt_sf_bn_relu_bwd_apply(L.ptr(gy.t), gy.ld, None, 0, None, None, L.ptr(r.y.t), r.y.ld, None, L.ptr(gx), gx.stride(0),
-                                                0, r.y.rows, r.y.C, L.stream_ptr()), "mt_sf_bn_relu_bwd_apply")
+        L.mt.sf_bn_relu_bwd_apply(gy.t, gy.ld, None, 0, None, None, r.y.t, r.y.ld, None, gx, gx.stride(0), 0, r.y.rows, r.y.C)
     ctx.add_wgrad(r.cc.key, r.zb, (r.bb.scale, r.bb.shift), dzc, r.cc)
     gb = torch.empty(r.zb.rows, r.zb.C, dtype=torch.float32, device=dev)
     conv_dgrad(r.zb, dzc, P[r.cc.key + ".weight"], r.cc, gb, False)
@@ -291,8 +281,7 @@ def _stem_fwd(ctx, key, x, kt, out):
     if out is None:
         out = torch.empty(rows, z.C, dtype=torch.float32, device=z.t.device)
     arg = torch.empty(rows, z.C, dtype=torch.int32, device=z.t.device)
-    L.check(L.get().mt_sf_maxpool_fwd(L.ptr(z.t), L.ptr(b.scale), L.ptr(b.shift), L.ptr(out), out.stride(0), L.ptr(arg), z.N * z.T, z.H,
-                                      z.W, z.C, L.stream_ptr()), "mt_sf_maxpool_fwd")
+    L.mt.sf_maxpool_fwd(z.t, b.scale, b.shift, out, out.stride(0), arg, z.N * z.T, z.H, z.W, z.C)
     return Fm(out, z.N, z.T, Ho, Wo), (conv, x, z, b, arg)
 
 
@@ -300,8 +289,7 @@ def _stem_bwd(ctx, rec, gp, want_dx=False):
     """Adjoint of the stem from gp = dL/d(pool output); want_dx: also returns dL/d(clip) as a packed [N, T, H, W, 4] tensor."""
     conv, x, z, b, arg = rec
     din = torch.empty(z.rows, z.C, dtype=torch.float32, device=z.t.device)
-    L.check(L.get().mt_sf_maxpool_bwd(L.ptr(gp.t), gp.ld, L.ptr(arg), L.ptr(din), z.N * z.T, z.H, z.W, z.C, L.stream_ptr()),
-            "mt_sf_maxpool_bwd")
+    L.mt.sf_maxpool_bwd(gp.t, gp.ld, arg, din, z.N * z.T, z.H, z.W, z.C)
     dz = bn_bwd(ctx, b, Fm(din, z.N, z.T, z.H, z.W), z, relu_bn=b, out=din)
     ctx.add_wgrad(conv.key, x, None, dz, conv)
     return stem_dgrad(x, dz, ctx.P[conv.key + ".weight"]) if want_dx else None
@@ -374,21 +362,18 @@ def network_forward(ctx, model, xs, xf):
     Pn = Pdims[0] * Pdims[1] * Pdims[2]
     mult = _dropout_mult(model, B, Pdims, dev)
     d = torch.empty(B, Pn, S.HEAD_DIM, dtype=torch.float32, device=dev)
-    lib = L.get()
     for feat, (kt, kh, kw), coff in ((xsl, (kts, khs, kws), 0), (xfa, (ktf, khf, kwf), S.SLOW_OUT[-1])):
-        L.check(lib.mt_sf_head_pool(L.ptr(feat.t), feat.ld, L.ptr(mult), L.ptr(d), B, feat.T, feat.H, feat.W, feat.C, kt, kh, kw, coff,
-                                    S.HEAD_DIM, L.stream_ptr()), "mt_sf_head_pool")
+        L.mt.sf_head_pool(feat.t, feat.ld, mult, d, B, feat.T, feat.H, feat.W, feat.C, kt, kh, kw, coff, S.HEAD_DIM)
     w, bias = P["proj.weight"], P["proj.bias"]
     J = w.shape[0]
     logits = torch.empty(B, J, dtype=torch.float32, device=dev)
-    L.check(lib.mt_sf_head_proj(L.ptr(d), L.ptr(w), L.ptr(bias), L.ptr(logits), B, Pn, S.HEAD_DIM, J, L.stream_ptr()), "mt_sf_head_proj")
+    L.mt.sf_head_proj(d, w, bias, logits, B, Pn, S.HEAD_DIM, J)
     recs["head"] = (xsl, xfa, d, mult, Pn, ((kts, khs, kws), (ktf, khf, kwf)))
     return logits, recs
 
 
 def network_backward(ctx, recs, g, need_x=(False, False)):
     """The reverse walk; need_x: return dL/d(packed slow clip), dL/d(packed fast clip) where asked for (else None)."""
-    lib = L.get()
     dev = g.device
     xsl, xfa, d, mult, Pn, ((kts, khs, kws), (ktf, khf, kwf)) = recs["head"]
     B, J = g.shape
@@ -396,13 +381,11 @@ def network_backward(ctx, recs, g, need_x=(False, False)):
     dpool = torch.empty(B, Pn, S.HEAD_DIM, dtype=torch.float32, device=dev)
     dw = ctx.grad_buf("proj.weight")
     db = ctx.grad_buf("proj.bias") if "proj.bias" in ctx.P else None
-    L.check(lib.mt_sf_head_bwd(L.ptr(g), L.ptr(d), L.ptr(w), L.ptr(mult), L.ptr(dw), L.ptr(db), L.ptr(dpool), B, Pn, S.HEAD_DIM, J,
-                               L.stream_ptr()), "mt_sf_head_bwd")
+    L.mt.sf_head_bwd(g, d, w, mult, dw, db, dpool, B, Pn, S.HEAD_DIM, J)
     gs = torch.empty(xsl.rows, xsl.C, dtype=torch.float32, device=dev)
     gf = torch.empty(xfa.rows, xfa.C, dtype=torch.float32, device=dev)
     for feat, gt, (kt, kh, kw), coff in ((xsl, gs, (kts, khs, kws), 0), (xfa, gf, (ktf, khf, kwf), S.SLOW_OUT[-1])):
-        L.check(lib.mt_sf_head_dfeat(L.ptr(dpool), L.ptr(gt), gt.stride(0), B, feat.T, feat.H, feat.W, feat.C, kt, kh, kw, coff, S.HEAD_DIM,
-                                     L.stream_ptr()), "mt_sf_head_dfeat")
+        L.mt.sf_head_dfeat(dpool, gt, gt.stride(0), B, feat.T, feat.H, feat.W, feat.C, kt, kh, kw, coff, S.HEAD_DIM)
     gsl = Fm(gs, xsl.N, xsl.T, xsl.H, xsl.W)
     gfa = Fm(gf, xfa.N, xfa.T, xfa.H, xfa.W)
     for s in reversed(range(4)):

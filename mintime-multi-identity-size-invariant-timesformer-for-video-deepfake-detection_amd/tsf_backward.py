@@ -14,8 +14,6 @@ from . import lib as L
 
 
 def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, need_dparams):
-    lib = L.get()
-    st = L.stream_ptr()
     dev = feat.device
     B, F, n = dims
     D, H, dh, C_in = model.dim, model.heads, model.dim_head, model.channels
@@ -42,7 +40,7 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
         side.wait(saved["wT_ready"])
 
     def colsum(A, lda, rows, cols, out, amap=(0, 0, 0)):
-        L.check(lib.mt_colsum(L.ptr(A), lda, L.RowMap(*amap), rows, cols, L.ptr(out), L.stream_ptr()), "mt_colsum")
+        L.mt.colsum(A, lda, L.RowMap(*amap), rows, cols, out)
 
     def dgrad(dY, Wm, off, out, N_, K_):
         """out[M, N_] = dY[M, K_] . Wm[K_, N_]: NT over the transposed weight (wT[(li, off)] = Wm^T [N_, K_]) if there is one, else NN."""
@@ -67,14 +65,11 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
         if ln_oop:
             dx_new = torch.empty_like(dx_cur)
             x_, st_ = r_["x"], r_["stats"]
-            L.check(lib.mt_layernorm_bwd_rows(L.ptr(dxn_), L.ptr(x_), L.ptr(st_), L.ptr(g_), L.ptr(dx_new), L.ptr(dx_cur), M, D, None, st),
-                    "mt_layernorm_bwd_rows")
-            side.launch(lambda: L.check(lib.mt_layernorm_bwd_cols(L.ptr(dxn_), L.ptr(x_), L.ptr(st_), L.ptr(dx_new), L.ptr(grads[i_g]),
-                                                                  L.ptr(grads[i_g + 1]), L.ptr(tgt), skip, M, D, L.stream_ptr()),
-                                        "mt_layernorm_bwd_cols"), reads=(dxn_, x_, st_, dx_new))
+            L.mt.layernorm_bwd_rows(dxn_, x_, st_, g_, dx_new, dx_cur, M, D, None)
+            side.launch(lambda: L.mt.layernorm_bwd_cols(dxn_, x_, st_, dx_new, grads[i_g], grads[i_g + 1], tgt, skip, M, D),
+                        reads=(dxn_, x_, st_, dx_new))
             return dx_new
-        L.check(lib.mt_layernorm_bwd(L.ptr(dxn_), L.ptr(r_["x"]), L.ptr(r_["stats"]), L.ptr(g_), L.ptr(dx_cur), L.ptr(grads[i_g]),
-                                     L.ptr(grads[i_g + 1]), M, D, 1, L.ptr(tgt), skip, None, st), "mt_layernorm_bwd")
+        L.mt.layernorm_bwd(dxn_, r_["x"], r_["stats"], g_, dx_cur, grads[i_g], grads[i_g + 1], M, D, 1, tgt, skip, None)
         return dx_cur
 
     # ---- head
@@ -83,9 +78,8 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
     pruned = bool(saved.get("pruned_last"))           # tsf_engine: the last layer ran its tail on the cls rows only
     Nh = 1 if pruned else N
     dx = torch.zeros(B, Nh, D, dtype=torch.float32, device=dev)
-    L.check(lib.mt_head_bwd(L.ptr(dlogits), L.ptr(saved["x_final"]), L.ptr(g), L.ptr(b_), L.ptr(w_h), L.ptr(dx), L.ptr(grads[i0]),
-                            L.ptr(grads[i0 + 1]), L.ptr(grads[i0 + 2]), L.ptr(grads[i0 + 3]), B, Nh, D, model.num_classes, eps,
-                            st), "mt_head_bwd")
+    L.mt.head_bwd(dlogits, saved["x_final"], g, b_, w_h, dx, grads[i0], grads[i0 + 1], grads[i0 + 2], grads[i0 + 3], B, Nh, D,
+                  model.num_classes, eps)
     dx2 = dx.view(B * Nh, D)
     # Bias gradients of the Linears whose output gradient is the residual stream's (net.3 / to_out.0 / patch embedding) are the
     # column sums of dx2 at that point.  The first one (last layer's net.3.bias) takes a column-sum launch over the head's dx;
@@ -119,8 +113,7 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
             wgrad(du_c, r["xn"], grads[i0 + 2], 8 * D, D, B, 8 * D, D, D)
             L.gemm(L.OP_NN, du_c, w1, dxn_c, B, D, 8 * D, 8 * D, D, D)
             side.wait()
-            L.check(lib.mt_layernorm_bwd(L.ptr(dxn_c), L.ptr(r["x"]), L.ptr(r["stats"]), L.ptr(g), L.ptr(dx2), L.ptr(grads[i0]),
-                                         L.ptr(grads[i0 + 1]), B, D, 1, L.ptr(grads[i0 - 1]), 0, None, st), "mt_layernorm_bwd")
+            L.mt.layernorm_bwd(dxn_c, r["x"], r["stats"], g, dx2, grads[i0], grads[i0 + 1], B, D, 1, grads[i0 - 1], 0, None)
             r.clear()
             # space attention: out-projection on the cls rows (row stride N), the cls query's adjoint, then the full QKV tail
             i0 = take(5)
@@ -129,8 +122,7 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
             wgrad(dx2, r["o"], grads[i0 + 3], D, inner, B, D, N * inner, inner)             # o's cls rows: ldb = N * inner
             L.gemm(L.OP_NN, dx2, w_o, do, B, inner, D, D, inner, N * inner)                 # row 0 of each clip's do; the rest is not read
             dqkv.zero_()                                                                    # the patch queries' gradients are zero
-            L.check(lib.mt_attn_bwd(L.ptr(r["qkv"]), L.ptr(do), L.ptr(dqkv), L.ptr(aux.mask), L.ptr(aux.ident), B, H, F, n, 2, scale, None, st),
-                    "mt_attn_bwd")
+            L.mt.attn_bwd(r["qkv"], do, dqkv, aux.mask, aux.ident, B, H, F, n, 2, scale, None)
             wgrad(dqkv, r["xn"], grads[i0 + 2], 3 * inner, D, M, 3 * inner, D, D)
             dgrad(dqkv, w_qkv, 7, dxn, D, 3 * inner)
             dx_full = torch.zeros(B, N, D, dtype=torch.float32, device=dev)
@@ -145,8 +137,7 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
             side.wait()
             e_dx = wgrad(dx2, r["o"], grads[i0 + 3], D, inner, M, D, inner, inner)
             dgrad(dx2, w_o, 3, do, inner, D)
-            L.check(lib.mt_attn_bwd(L.ptr(r["qkv"]), L.ptr(do), L.ptr(dqkv), L.ptr(aux.mask), L.ptr(aux.ident), B, H, F, n, 0, scale, None, st),
-                    "mt_attn_bwd")
+            L.mt.attn_bwd(r["qkv"], do, dqkv, aux.mask, aux.ident, B, H, F, n, 0, scale, None)
             wgrad(dqkv, r["xn"], grads[i0 + 2], 3 * inner, D, M, 3 * inner, D, D)
             dgrad(dqkv, w_qkv, 2, dxn, D, 3 * inner)
             if join_each:
@@ -190,8 +181,7 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
                 dxn = torch.empty(M, D, dtype=torch.float32, device=dev)
             e_dx = wgrad(dx2, r["o"], grads[i0 + 3], D, inner, M, D, inner, inner)
             dgrad(dx2, w_o, 8 if mode == 1 else 3, do, inner, D)
-            L.check(lib.mt_attn_bwd(L.ptr(r["qkv"]), L.ptr(do), L.ptr(dqkv), L.ptr(aux.mask), L.ptr(aux.ident), B, H, F, n, mode,
-                                    scale, None, st), "mt_attn_bwd")
+            L.mt.attn_bwd(r["qkv"], do, dqkv, aux.mask, aux.ident, B, H, F, n, mode, scale, None)
             wgrad(dqkv, r["xn"], grads[i0 + 2], 3 * inner, D, M, 3 * inner, D, D)
             dgrad(dqkv, w_qkv, 7 if mode == 1 else 2, dxn, D, 3 * inner)
             if join_each:
@@ -210,9 +200,8 @@ def tsf_backward(model, feat, aux, params, dims, saved, dlogits, need_dfeat, nee
     i0 = take(5)
     w_pe, b_pe, cls, pos_w, size_w = P[i0:i0 + 5]
     dx = dx2.view(B, N, D)
-    L.check(lib.mt_embed_bwd(L.ptr(dx), L.ptr(grads[i0 + 2]), L.ptr(grads[i0 + 3]), L.ptr(grads[i0 + 4]), L.ptr(aux.positions),
-                             L.ptr(aux.sizes), B, F, n, D, pos_w.shape[0], size_w.shape[0] if size_w is not None else 0, st),
-            "mt_embed_bwd")
+    L.mt.embed_bwd(dx, grads[i0 + 2], grads[i0 + 3], grads[i0 + 4], aux.positions, aux.sizes, B, F, n, D, pos_w.shape[0],
+                   size_w.shape[0] if size_w is not None else 0)
     tok_map = (F * n, N, 1)      # token row r of the feature matrix lives at row (r/(F n))*N + 1 + r%(F n) of dx
     Mt = B * F * n
     side.wait()

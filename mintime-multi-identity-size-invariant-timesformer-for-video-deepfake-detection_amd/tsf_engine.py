@@ -96,8 +96,6 @@ def _publish_index_flag(state):
 
 def tsf_forward(model, feat, aux, params, B, F, n, save):
     """Runs the forward launch sequence.  Returns (logits, space_att, time_att, saved-dict or None)."""
-    lib = L.get()
-    st = L.stream_ptr()
     dev = feat.device
     D, H, dh, C_in = model.dim, model.heads, model.dim_head, model.channels
     inner = H * dh
@@ -110,9 +108,8 @@ def tsf_forward(model, feat, aux, params, B, F, n, save):
 
     x = _new(dev, B, N, D)
     L.gemm(L.OP_NT, feat, w_pe, x, B * F * n, D, C_in, C_in, C_in, D, bias=b_pe, c_map=(F * n, N, 1))
-    L.check(lib.mt_embed_fwd(L.ptr(x), L.ptr(cls), L.ptr(pos_w), L.ptr(size_w), L.ptr(aux.positions), L.ptr(aux.sizes),
-                             B, F, n, D, pos_w.shape[0], size_w.shape[0] if size_w is not None else 0, L.ptr(aux.err[0]), st),
-            "mt_embed_fwd")
+    L.mt.embed_fwd(x, cls, pos_w, size_w, aux.positions, aux.sizes, B, F, n, D, pos_w.shape[0],
+                   size_w.shape[0] if size_w is not None else 0, aux.err[0])
     _publish_index_flag(aux.err)
 
     saved = {"layers": []} if save else None
@@ -146,8 +143,7 @@ def tsf_forward(model, feat, aux, params, B, F, n, save):
             model._wT_cache = cache
 
         def transpose_all():
-            L.check(lib.mt_transpose_multi(cache["table"].data_ptr(), cache["count"], cache["tiles"], L.stream_ptr()),
-                    "mt_transpose_multi")
+            L.mt.transpose_multi(cache["table"], cache["count"], cache["tiles"])
         if side.enabled:       # with MT_SIDE_STREAM=0 the transposes would sit on the critical path: the NN form is used instead
             cache["serial"] = cache.get("serial", 0) + 1       # a later forward rewrites the buffers: backward checks this
             saved["wT"], saved["wT_ready"], saved["wT_serial"] = cache["holder"], side.launch(transpose_all, reads=wts), cache["serial"]
@@ -174,7 +170,7 @@ def tsf_forward(model, feat, aux, params, B, F, n, save):
                 stats = _new(dev, M, 2)
             else:
                 stats = None
-            L.check(lib.mt_layernorm_fwd(L.ptr(x), L.ptr(g), L.ptr(b_), L.ptr(xn), L.ptr(stats), M, D, eps, None, st), "mt_layernorm_fwd")
+            L.mt.layernorm_fwd(x, g, b_, xn, stats, M, D, eps, None)
             L.gemm(L.OP_NT, xn, w_qkv, qkv, M, 3 * inner, D, D, D, 3 * inner)
             att = None
             if want_att and last:
@@ -185,16 +181,14 @@ def tsf_forward(model, feat, aux, params, B, F, n, save):
                     s_att = att
             if last and mode == 1 and prune_last:
                 # cls query only; out-projection + residual on the B cls rows (row stride N: no gather needed)
-                L.check(lib.mt_attn_fwd(L.ptr(qkv), L.ptr(o), L.ptr(att), L.ptr(aux.mask), L.ptr(aux.ident), B, H, F, n, 2,
-                                        scale, None, st), "mt_attn_fwd")
+                L.mt.attn_fwd(qkv, o, att, aux.mask, aux.ident, B, H, F, n, 2, scale, None)
                 x_cls = _new(dev, B, D)
                 L.gemm(L.OP_NT, o, w_o, x_cls, B, D, inner, N * inner, inner, D, epilogue=L.EPI_BIAS_RES, bias=b_o, R=x, ldr=N * D)
                 if save:
                     rec[mode] = dict(x=x, xn=xn, stats=stats, qkv=qkv, o=o)
                 x = x_cls
                 continue
-            L.check(lib.mt_attn_fwd(L.ptr(qkv), L.ptr(o), L.ptr(att), L.ptr(aux.mask), L.ptr(aux.ident), B, H, F, n, mode,
-                                    scale, None, st), "mt_attn_fwd")
+            L.mt.attn_fwd(qkv, o, att, aux.mask, aux.ident, B, H, F, n, mode, scale, None)
             x_new = _new(dev, B, N, D) if save else x
             L.gemm(L.OP_NT, o, w_o, x_new, M, D, inner, inner, inner, D, epilogue=L.EPI_BIAS_RES, bias=b_o, R=x, ldr=D)
             if save:
@@ -205,7 +199,7 @@ def tsf_forward(model, feat, aux, params, B, F, n, save):
             # feed-forward block on the cls rows only (x is [B, D] here)
             xn_c, h_c, stats_c = _new(dev, B, D), _new(dev, B, 4 * D), (_new(dev, B, 2) if save else None)
             u_c = _new(dev, B, 8 * D) if save else None
-            L.check(lib.mt_layernorm_fwd(L.ptr(x), L.ptr(g), L.ptr(b_), L.ptr(xn_c), L.ptr(stats_c), B, D, eps, None, st), "mt_layernorm_fwd")
+            L.mt.layernorm_fwd(x, g, b_, xn_c, stats_c, B, D, eps, None)
             L.gemm(L.OP_NT, xn_c, w1, h_c, B, 8 * D, D, D, D, 4 * D, epilogue=L.EPI_GEGLU, bias=b1, C2=u_c, ldc2=8 * D, n_half=4 * D)
             x_out = _new(dev, B, 1, D)
             L.gemm(L.OP_NT, h_c, w2, x_out, B, D, 4 * D, 4 * D, 4 * D, D, epilogue=L.EPI_BIAS_RES, bias=b2, R=x, ldr=D)
@@ -220,7 +214,7 @@ def tsf_forward(model, feat, aux, params, B, F, n, save):
             u = _new(dev, M, 8 * D)
         else:
             stats, u = None, None
-        L.check(lib.mt_layernorm_fwd(L.ptr(x), L.ptr(g), L.ptr(b_), L.ptr(xn), L.ptr(stats), M, D, eps, None, st), "mt_layernorm_fwd")
+        L.mt.layernorm_fwd(x, g, b_, xn, stats, M, D, eps, None)
         L.gemm(L.OP_NT, xn, w1, hbuf, M, 8 * D, D, D, D, 4 * D, epilogue=L.EPI_GEGLU, bias=b1, C2=u, ldc2=8 * D, n_half=4 * D)
         x_new = _new(dev, B, N, D) if save else x
         L.gemm(L.OP_NT, hbuf, w2, x_new, M, D, 4 * D, 4 * D, 4 * D, D, epilogue=L.EPI_BIAS_RES, bias=b2, R=x, ldr=D)
@@ -230,8 +224,7 @@ def tsf_forward(model, feat, aux, params, B, F, n, save):
         x = x_new
     g, b_, w_h, b_h = next(it), next(it), next(it), next(it)
     logits = _new(dev, B, model.num_classes)
-    L.check(lib.mt_head_fwd(L.ptr(x), L.ptr(g), L.ptr(b_), L.ptr(w_h), L.ptr(b_h), L.ptr(logits), B, x.shape[1], D, model.num_classes,
-                            eps, st), "mt_head_fwd")        # x: [B, N, D], or [B, 1, D] after dead-row pruning
+    L.mt.head_fwd(x, g, b_, w_h, b_h, logits, B, x.shape[1], D, model.num_classes, eps)    # x: [B, N, D], or [B, 1, D] after pruning
     if save:
         saved["x_final"] = x
     return logits, s_att, t_att, saved

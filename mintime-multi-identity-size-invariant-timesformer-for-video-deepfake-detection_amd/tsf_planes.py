@@ -53,7 +53,6 @@ def _dropout_mult(model, shape, p, dev):
 def weight_planes(model, params, training):
     """Plane tensors of the 6 Linear weights of every layer, kept on the module (their storage is allocated once) and re-split from
     the fp32 weights at the start of every forward."""
-    lib = L.get()
     wts = list(params[5:5 + 16 * model.depth])
     sel = [(li, off) for li in range(model.depth) for off in _SEL]
     ws = [wts[16 * li + off] for li, off in sel]
@@ -76,16 +75,13 @@ def weight_planes(model, params, training):
     # The planes are re-written on EVERY forward (one launch, ~60 us for the 54 matrices): updates that move no version counter
     # (p.data.copy_, dist.broadcast(p.data), a fused optimizer step through raw pointers) cannot leave them stale, and a forward
     # captured into a HIP graph (harness.GraphedEval) holds the split as a node, so its replays read the weights of the replay's time.
-    L.check(lib.mt_split_planes_blk_multi(L.ptr(cache["table"]), cache["count"], cache["blocks"], L.stream_ptr()),
-            "mt_split_planes_blk_multi")             # (L.ptr: a launch plan being recorded pins the table)
+    L.mt.split_planes_blk_multi(cache["table"], cache["count"], cache["blocks"])      # (a launch plan being recorded pins the table)
     return cache["holder"], cache["serial"].touch(ws)
 
 
 def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
     """Forward launch sequence on plane operands.  Returns (logits, space_att, time_att, saved-dict or None)."""
     from .tsf_engine import _publish_index_flag
-    lib = L.get()
-    st = L.stream_ptr()
     dev = feat.device
     D, H, dh, C_in = model.dim, model.heads, model.dim_head, model.channels
     inner = H * dh
@@ -99,9 +95,8 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
 
     x = _new(dev, B, N, D)
     L.gemm(L.OP_NT, feat, w_pe, x, B * F * n, D, C_in, C_in, C_in, D, bias=b_pe, c_map=(F * n, N, 1))
-    L.check(lib.mt_embed_fwd(L.ptr(x), L.ptr(cls), L.ptr(pos_w), L.ptr(size_w), L.ptr(aux.positions), L.ptr(aux.sizes),
-                             B, F, n, D, pos_w.shape[0], size_w.shape[0] if size_w is not None else 0, L.ptr(aux.err[0]), st),
-            "mt_embed_fwd")
+    L.mt.embed_fwd(x, cls, pos_w, size_w, aux.positions, aux.sizes, B, F, n, D, pos_w.shape[0],
+                   size_w.shape[0] if size_w is not None else 0, aux.err[0])
     _publish_index_flag(aux.err)
 
     saved = {"layers": [], "planes": True, "wp": wp, "w_serial": serial} if save else None
@@ -123,7 +118,7 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
                 stats = _new(dev, M, 2)
             else:
                 stats = None
-            L.check(lib.mt_layernorm_fwd(L.ptr(x), L.ptr(g), L.ptr(b_), None, L.ptr(stats), M, D, eps, L.ptr(xn_p), st), "mt_layernorm_fwd")
+            L.mt.layernorm_fwd(x, g, b_, None, stats, M, D, eps, xn_p)
             L.gemm_planes(L.OP_NT, xn_p, wp[(li, 2 if mode == 0 else 7)], M, 3 * inner, D, Cout=qkv, ldc=3 * inner)
             att = None
             if want_att and last:
@@ -132,8 +127,7 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
                     t_att = att
                 else:
                     s_att = att
-            L.check(lib.mt_attn_fwd(L.ptr(qkv), None, L.ptr(att), L.ptr(aux.mask), L.ptr(aux.ident), B, H, F, n, mode,
-                                    scale, L.ptr(o_p), st), "mt_attn_fwd")      # o leaves the attention kernels as planes only
+            L.mt.attn_fwd(qkv, None, att, aux.mask, aux.ident, B, H, F, n, mode, scale, o_p)      # o leaves the kernels as planes only
             x_new = _new(dev, B, N, D) if save else x
             dm = None
             if p_att > 0.0:
@@ -141,7 +135,7 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
                 dm = _dropout_mult(model, (M, D), p_att, dev)
                 y0 = _new(dev, M, D)
                 L.gemm_planes(L.OP_NT, o_p, wp[(li, 3 if mode == 0 else 8)], M, D, inner, Cout=y0, ldc=D, bias=b_o)
-                L.check(lib.mt_mul_add(L.ptr(y0), L.ptr(dm), L.ptr(x), L.ptr(x_new), M * D, st), "mt_mul_add")
+                L.mt.mul_add(y0, dm, x, x_new, M * D)
             else:
                 L.gemm_planes(L.OP_NT, o_p, wp[(li, 3 if mode == 0 else 8)], M, D, inner, Cout=x_new, ldc=D, epilogue=L.EPI_BIAS_RES,
                               bias=b_o, R=x, ldr=D)
@@ -154,7 +148,7 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
             u = _new(dev, M, 8 * D)
         else:
             stats, u = None, None
-        L.check(lib.mt_layernorm_fwd(L.ptr(x), L.ptr(g), L.ptr(b_), None, L.ptr(stats), M, D, eps, L.ptr(xn_p), st), "mt_layernorm_fwd")
+        L.mt.layernorm_fwd(x, g, b_, None, stats, M, D, eps, xn_p)
         dm = None
         if p_ff > 0.0:
             # net = Linear, GEGLU, Dropout, Linear: h leaves the GEGLU epilogue as fp32, its planes are those of h * m
@@ -162,7 +156,7 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
             h = _new(dev, M, 4 * D)
             L.gemm_planes(L.OP_NT, xn_p, wp[(li, 12)], M, 8 * D, D, epilogue=L.EPI_GEGLU, bias=b1, C2=u, ldc2=8 * D, n_half=4 * D,
                           Cout=h, ldc=4 * D)
-            L.check(lib.mt_mul_planes(L.ptr(h), L.ptr(dm), L.ptr(h_p), None, M, 4 * D, st), "mt_mul_planes")
+            L.mt.mul_planes(h, dm, h_p, None, M, 4 * D)
             del h
         else:
             L.gemm_planes(L.OP_NT, xn_p, wp[(li, 12)], M, 8 * D, D, epilogue=L.EPI_GEGLU, bias=b1, C2=u, ldc2=8 * D, n_half=4 * D,
@@ -175,8 +169,7 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
         x = x_new
     g, b_, w_h, b_h = next(it), next(it), next(it), next(it)
     logits = _new(dev, B, model.num_classes)
-    L.check(lib.mt_head_fwd(L.ptr(x), L.ptr(g), L.ptr(b_), L.ptr(w_h), L.ptr(b_h), L.ptr(logits), B, x.shape[1], D, model.num_classes,
-                            eps, st), "mt_head_fwd")
+    L.mt.head_fwd(x, g, b_, w_h, b_h, logits, B, x.shape[1], D, model.num_classes, eps)
     if save:
         saved["x_final"] = x
     return logits, s_att, t_att, saved
@@ -188,7 +181,6 @@ def tsf_backward_planes(model, feat, aux, params, dims, saved, dlogits, need_dfe
     of the LayerNorm backward on the weight-gradient stream.  Every sub-block writes its gradients into fresh buffers that the side
     launches pin, so the main stream waits for nothing inside the layer loop (tsf_backward.py)."""
     lib = L.get()
-    st = L.stream_ptr()
     dev = feat.device
     B, F, n = dims
     D, H, dh, C_in = model.dim, model.heads, model.dim_head, model.channels
@@ -214,7 +206,7 @@ def tsf_backward_planes(model, feat, aux, params, dims, saved, dlogits, need_dfe
         def run():
             L.gemm_planes(L.OP_TN, a_p, b_p, M_, N_, M, Cout=out, ldc=N_, epilogue=L.EPI_ATOMIC)
             if bias_out is not None:
-                L.check(lib.mt_colsum(L.ptr(bias_src), D, L.RowMap(0, 0, 0), M, D, L.ptr(bias_out), L.stream_ptr()), "mt_colsum")
+                L.mt.colsum(bias_src, D, L.RowMap(0, 0, 0), M, D, bias_out)
         return side.launch(run, reads=(a_p, b_p, bias_src))
 
     def ln_bwd(dxn_, r_, g_, dx_cur, i_g, tgt, skip):
@@ -227,27 +219,21 @@ def tsf_backward_planes(model, feat, aux, params, dims, saved, dlogits, need_dfe
             # the rows kernel also leaves per-block partial column sums; the weight-gradient stream only adds 6 MB of them up
             nb = lib.mt_layernorm_bwd_rows_blocks(M)
             part = _new(dev, nb, 3, D)
-            L.check(lib.mt_layernorm_bwd_rows_sums(L.ptr(dxn_), L.ptr(x_), L.ptr(st_), L.ptr(g_), L.ptr(dx_new), L.ptr(dx_cur), M, D,
-                                                   L.ptr(dx_p), L.ptr(part), skip, st), "mt_layernorm_bwd_rows_sums")
-            side.launch(lambda: L.check(lib.mt_layernorm_bwd_cols_reduce(L.ptr(part), nb, D, L.ptr(grads[i_g]), L.ptr(grads[i_g + 1]),
-                                                                         L.ptr(tgt), L.stream_ptr()), "mt_layernorm_bwd_cols_reduce"),
-                        reads=(part,))
+            L.mt.layernorm_bwd_rows_sums(dxn_, x_, st_, g_, dx_new, dx_cur, M, D, dx_p, part, skip)
+            side.launch(lambda: L.mt.layernorm_bwd_cols_reduce(part, nb, D, grads[i_g], grads[i_g + 1], tgt), reads=(part,))
             return dx_new, dx_p
         # wider rows: the column sums are a second pass over dy / x / dx on the weight-gradient stream
-        L.check(lib.mt_layernorm_bwd_rows(L.ptr(dxn_), L.ptr(x_), L.ptr(st_), L.ptr(g_), L.ptr(dx_new), L.ptr(dx_cur), M, D,
-                                          L.ptr(dx_p), st), "mt_layernorm_bwd_rows")
-        side.launch(lambda: L.check(lib.mt_layernorm_bwd_cols(L.ptr(dxn_), L.ptr(x_), L.ptr(st_), L.ptr(dx_new), L.ptr(grads[i_g]),
-                                                              L.ptr(grads[i_g + 1]), L.ptr(tgt), skip, M, D, L.stream_ptr()),
-                                    "mt_layernorm_bwd_cols"), reads=(dxn_, x_, st_, dx_new))
+        L.mt.layernorm_bwd_rows(dxn_, x_, st_, g_, dx_new, dx_cur, M, D, dx_p)
+        side.launch(lambda: L.mt.layernorm_bwd_cols(dxn_, x_, st_, dx_new, grads[i_g], grads[i_g + 1], tgt, skip, M, D),
+                    reads=(dxn_, x_, st_, dx_new))
         return dx_new, dx_p
 
     # ---- head
     i0 = take(4)
     g, b_, w_h, b_h = P[i0:i0 + 4]
     dx = L.zeros((B, N, D), torch.float32, dev)
-    L.check(lib.mt_head_bwd(L.ptr(dlogits), L.ptr(saved["x_final"]), L.ptr(g), L.ptr(b_), L.ptr(w_h), L.ptr(dx), L.ptr(grads[i0]),
-                            L.ptr(grads[i0 + 1]), L.ptr(grads[i0 + 2]), L.ptr(grads[i0 + 3]), B, N, D, model.num_classes, eps,
-                            st), "mt_head_bwd")
+    L.mt.head_bwd(dlogits, saved["x_final"], g, b_, w_h, dx, grads[i0], grads[i0 + 1], grads[i0 + 2], grads[i0 + 3], B, N, D,
+                  model.num_classes, eps)
     dx2 = dx.view(M, D)
     dx_p = L.split_planes_blk(dx2, M, D)
     do = torch.empty(M, inner, dtype=torch.float32, device=dev)
@@ -267,9 +253,8 @@ def tsf_backward_planes(model, feat, aux, params, dims, saved, dlogits, need_dfe
             # ff-dropout: dh = (dx W2) * m, then GEGLU' as a pass (the fused epilogue has no multiplier); bias gradient = column sums of du
             dh, du_f = torch.empty(M, 4 * D, dtype=torch.float32, device=dev), torch.empty(M, 8 * D, dtype=torch.float32, device=dev)
             L.gemm_planes(L.OP_NN, dx_p, wp[(li, 14)], M, 4 * D, D, Cout=dh, ldc=4 * D)
-            L.check(lib.mt_geglu_bwd(L.ptr(dh), L.ptr(r["dm"]), L.ptr(r["u"]), L.ptr(du_p), L.ptr(du_f), M, 4 * D, st), "mt_geglu_bwd")
-            side.launch(lambda du_f=du_f, out=grads[i0 + 3]: L.check(lib.mt_colsum(L.ptr(du_f), 8 * D, L.RowMap(0, 0, 0), M, 8 * D,
-                                                                                 L.ptr(out), L.stream_ptr()), "mt_colsum"), reads=(du_f,))
+            L.mt.geglu_bwd(dh, r["dm"], r["u"], du_p, du_f, M, 4 * D)
+            side.launch(lambda du_f=du_f, out=grads[i0 + 3]: L.mt.colsum(du_f, 8 * D, L.RowMap(0, 0, 0), M, 8 * D, out), reads=(du_f,))
             del dh
         else:
             L.gemm_planes(L.OP_NN, dx_p, wp[(li, 14)], M, 4 * D, D, epilogue=L.EPI_GEGLU_BWD, C2=r["u"], ldc2=8 * D, n_half=4 * D,
@@ -292,14 +277,12 @@ def tsf_backward_planes(model, feat, aux, params, dims, saved, dlogits, need_dfe
                 # attn-dropout: d(o Wo^T + b) = dx * m -- as planes for both GEMMs, as fp32 for the bias gradient's column sums
                 dy_p = L.planes_empty(M, D, dev)
                 dy_f = torch.empty(M, D, dtype=torch.float32, device=dev)
-                L.check(lib.mt_mul_planes(L.ptr(dx2), L.ptr(r["dm"]), L.ptr(dy_p), L.ptr(dy_f), M, D, st), "mt_mul_planes")
-                side.launch(lambda dy_f=dy_f, out=grads[i0 + 4]: L.check(lib.mt_colsum(L.ptr(dy_f), D, L.RowMap(0, 0, 0), M, D, L.ptr(out),
-                                                                                     L.stream_ptr()), "mt_colsum"), reads=(dy_f,))
+                L.mt.mul_planes(dx2, r["dm"], dy_p, dy_f, M, D)
+                side.launch(lambda dy_f=dy_f, out=grads[i0 + 4]: L.mt.colsum(dy_f, D, L.RowMap(0, 0, 0), M, D, out), reads=(dy_f,))
             wgrad(dy_p, r["o_p"], grads[i0 + 3], D, inner)
             L.gemm_planes(L.OP_NN, dy_p, wp[(li, 8 if mode == 1 else 3)], M, inner, D, Cout=do, ldc=inner)
             dqkv_p = L.planes_empty(M, 3 * inner, dev)
-            L.check(lib.mt_attn_bwd(L.ptr(r["qkv"]), L.ptr(do), L.ptr(dqkv), L.ptr(aux.mask), L.ptr(aux.ident), B, H, F, n, mode,
-                                    scale, L.ptr(dqkv_p), st), "mt_attn_bwd")    # dqkv (fp32) is working memory here
+            L.mt.attn_bwd(r["qkv"], do, dqkv, aux.mask, aux.ident, B, H, F, n, mode, scale, dqkv_p)    # dqkv (fp32) is working memory here
             wgrad(dqkv_p, r["xn_p"], grads[i0 + 2], 3 * inner, D)
             L.gemm_planes(L.OP_NN, dqkv_p, wp[(li, 7 if mode == 1 else 2)], M, D, 3 * inner, Cout=dxn, ldc=D)
             # the updated dx feeds the sub-block below: time attention's to_out.0.bias (index i0 - 1), the previous layer's
@@ -319,9 +302,8 @@ def tsf_backward_planes(model, feat, aux, params, dims, saved, dlogits, need_dfe
     i0 = take(5)
     w_pe, b_pe, cls, pos_w, size_w = P[i0:i0 + 5]
     dx = dx2.view(B, N, D)
-    L.check(lib.mt_embed_bwd(L.ptr(dx), L.ptr(grads[i0 + 2]), L.ptr(grads[i0 + 3]), L.ptr(grads[i0 + 4]), L.ptr(aux.positions),
-                             L.ptr(aux.sizes), B, F, n, D, pos_w.shape[0], size_w.shape[0] if size_w is not None else 0, st),
-            "mt_embed_bwd")
+    L.mt.embed_bwd(dx, grads[i0 + 2], grads[i0 + 3], grads[i0 + 4], aux.positions, aux.sizes, B, F, n, D, pos_w.shape[0],
+                   size_w.shape[0] if size_w is not None else 0)
     tok_map = (F * n, N, 1)
     Mt = B * F * n
     side.launch(lambda: L.gemm(L.OP_TN, dx2, feat, grads[i0], D, C_in, Mt, D, C_in, C_in, epilogue=L.EPI_ATOMIC, split_k=0, a_map=tok_map),

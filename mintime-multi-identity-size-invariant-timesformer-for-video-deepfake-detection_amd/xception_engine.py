@@ -89,8 +89,7 @@ class _WeightPlanes:
         if any(w.data_ptr() != k for k, (w, _, _, _) in self.items.items()):       # a weight moved: start over
             self.items, self.table = {}, None
             return
-        L.check(lib.mt_split_planes_blk_multi(L.ptr(self.table), len(self.items), self.blocks, L.stream_ptr()),
-                "mt_split_planes_blk_multi")
+        L.mt.split_planes_blk_multi(self.table, len(self.items), self.blocks)
         self.fresh = True
 
     def get(self, w_pw, co, ci):
@@ -133,7 +132,7 @@ def xception_forward(model, x, params, training, save, plan=None):
 
     def pack(w, Co, Ci, k, ld, transpose=0):
         out = _new(dev, Ci if transpose else Co, ld)
-        L.check(lib.mt_conv_weight_pack(L.ptr(w), L.ptr(out), Co, Ci, k, ld, transpose, L.stream_ptr()), "mt_conv_weight_pack")
+        L.mt.conv_weight_pack(w, out, Co, Ci, k, ld, transpose)
         return out
 
     def conv_im2col(src, wp, Cout, K, geom, bn_mod, gamma, beta, u8=False):
@@ -144,7 +143,7 @@ def xception_forward(model, x, params, training, save, plan=None):
         z = _new(dev, M, Cout)
         L.gemm(L.OP_NT, src.t, wp, z, M, Cout, K, K, K, Cout, prologue=L.PRO_IM2COL, epilogue=epi, scale=src.scale, shift=src.shift,
                stats=ctx.stats, stats_slots=slots, conv=(Hh, Ww, Cc, Ho, Wo, k, s_, p_, src.act, 1 if u8 else 0))
-        _finalize(lib, bn_mod, ctx, M, training, gamma, beta, slots)
+        _finalize(bn_mod, ctx, M, training, gamma, beta, slots)
         return z, ctx
 
     def sep_unit(src, act, w_dw, w_pw, co, bn_mod, gamma, beta):
@@ -162,22 +161,19 @@ def xception_forward(model, x, params, training, save, plan=None):
             # forward; the depthwise kernel writes its output as planes and nowhere else (DW_PLANES; round 4: fp32 + a split pass)
             d_p = L.planes_empty(M, ci, dev)
             if DW_PLANES:
-                L.check(lib.mt_dwconv_fwd_planes(L.ptr(src.t), L.ptr(sc), L.ptr(sh), L.ptr(w_dw), L.ptr(d_p), N, Hh, Hh, ci, 3, 1, eff,
-                                                 L.stream_ptr()), "mt_dwconv_fwd_planes")
+                L.mt.dwconv_fwd_planes(src.t, sc, sh, w_dw, d_p, N, Hh, Hh, ci, 3, 1, eff)
             else:
                 d = _new(dev, M, ci)
-                L.check(lib.mt_dwconv_fwd(L.ptr(src.t), L.ptr(sc), L.ptr(sh), L.ptr(w_dw), L.ptr(d), None, SLOTS, N, Hh, Hh, ci, 3, 1, eff,
-                                          L.stream_ptr()), "mt_dwconv_fwd")
+                L.mt.dwconv_fwd(src.t, sc, sh, w_dw, d, None, SLOTS, N, Hh, Hh, ci, 3, 1, eff)
                 L.split_planes_blk(d, M, ci, out=d_p)
                 d = None                                   # backward reads d through its planes only
             w_p = wplanes.get(w_pw, co, ci)
             L.gemm_planes(L.OP_NT, d_p, w_p, M, co, ci, Cout=z, ldc=co, epilogue=epi, stats=ctx.stats, stats_slots=slots)
         else:
             d = _new(dev, M, ci)
-            L.check(lib.mt_dwconv_fwd(L.ptr(src.t), L.ptr(sc), L.ptr(sh), L.ptr(w_dw), L.ptr(d), None, SLOTS, N, Hh, Hh, ci, 3, 1, eff,
-                                      L.stream_ptr()), "mt_dwconv_fwd")
+            L.mt.dwconv_fwd(src.t, sc, sh, w_dw, d, None, SLOTS, N, Hh, Hh, ci, 3, 1, eff)
             L.gemm(L.OP_NT, d, w_pw, z, M, co, ci, ci, ci, co, epilogue=epi, stats=ctx.stats, stats_slots=slots)
-        _finalize(lib, bn_mod, ctx, M, training, gamma, beta, slots)
+        _finalize(bn_mod, ctx, M, training, gamma, beta, slots)
         rec = dict(src=src, eff=eff, sc=sc, sh=sh, d=d, d_p=d_p, w_p=w_p, z=z, bn=ctx, ci=ci, co=co, H=Hh) if save else None
         return _Src(z, co, Hh, ctx.scale, ctx.shift, NONE, ctx), rec
 
@@ -189,9 +185,8 @@ def xception_forward(model, x, params, training, save, plan=None):
         # against 0.5 at 512 crops); reads uint8 crops as well
         bn1 = _BNCtx(dev, 32, training, pool)
         z1 = _new(dev, N * H1 * H1, 32)
-        L.check(lib.mt_stem_conv_fwd_valid(L.ptr(x), 1 if x.dtype == torch.uint8 else 0, L.ptr(w1), L.ptr(z1), L.ptr(bn1.stats) if training
-                                           else None, slots, N, H, W, L.stream_ptr()), "mt_stem_conv_fwd_valid")
-        _finalize(lib, model.bn1, bn1, N * H1 * H1, training, g1, b1, slots)
+        L.mt.stem_conv_fwd_valid(x, 1 if x.dtype == torch.uint8 else 0, w1, z1, bn1.stats if training else None, slots, N, H, W)
+        _finalize(model.bn1, bn1, N * H1 * H1, training, g1, b1, slots)
     else:
         wp1 = pack(w1, 32, 3, 3, 28)
         z1, bn1 = conv_im2col(_Src(x, 3, H), wp1, 32, 28, (H, W, 3, H1, H1, 3, 2, 0), model.bn1, g1, b1, u8=x.dtype == torch.uint8)
@@ -226,19 +221,15 @@ def xception_forward(model, x, params, training, save, plan=None):
                 # full-resolution routed gradient by atomics, and takes the pooled unit's BatchNorm sums from the pooled tensors
                 arg = torch.empty(N * Ho * Ho, cout, dtype=torch.uint8, device=dev)
                 zmax = _new(dev, N * Ho * Ho, cout)
-                L.check(lib.mt_maxpool_add_fwd_arg(L.ptr(src.t), L.ptr(src.scale), L.ptr(src.shift), L.ptr(z_s), L.ptr(bn_s.scale),
-                                                   L.ptr(bn_s.shift), L.ptr(y), L.ptr(arg), L.ptr(zmax), N, Hin, Hin, cout, L.stream_ptr()),
-                        "mt_maxpool_add_fwd_arg")
+                L.mt.maxpool_add_fwd_arg(src.t, src.scale, src.shift, z_s, bn_s.scale, bn_s.shift, y, arg, zmax, N, Hin, Hin, cout)
                 brec.update(arg=arg, zmax=zmax)
             else:
-                L.check(lib.mt_maxpool_add_fwd(L.ptr(src.t), L.ptr(src.scale), L.ptr(src.shift), L.ptr(z_s), L.ptr(bn_s.scale),
-                                               L.ptr(bn_s.shift), L.ptr(y), N, Hin, Hin, cout, L.stream_ptr()), "mt_maxpool_add_fwd")
+                L.mt.maxpool_add_fwd(src.t, src.scale, src.shift, z_s, bn_s.scale, bn_s.shift, y, N, Hin, Hin, cout)
             brec.update(z_s=z_s, bn_s=bn_s, Ho=Ho)
             cur = _Src(y, cout, Ho)
         else:
             y = _new(dev, N * Hin * Hin, cout)
-            L.check(lib.mt_bn_act_fwd(L.ptr(src.t), L.ptr(src.scale), L.ptr(src.shift), L.ptr(inp.t), L.ptr(y), N * Hin * Hin, cout, 0,
-                                      None, 1, L.stream_ptr()), "mt_bn_act_fwd")
+            L.mt.bn_act_fwd(src.t, src.scale, src.shift, inp.t, y, N * Hin * Hin, cout, 0, None, 1)
             cur = _Src(y, cout, Hin)
         if save:
             saved["blocks"].append(brec)
@@ -251,8 +242,7 @@ def xception_forward(model, x, params, training, save, plan=None):
         tail.append(rec)
     M = N * cur.H * cur.H
     feat = _new(dev, M, 2048)
-    L.check(lib.mt_bn_act_fwd(L.ptr(cur.t), L.ptr(cur.scale), L.ptr(cur.shift), None, L.ptr(feat), M, 2048, 0, None, 1, L.stream_ptr()),
-            "mt_bn_act_fwd")
+    L.mt.bn_act_fwd(cur.t, cur.scale, cur.shift, None, feat, M, 2048, 0, None, 1)
     if save:
         saved["tail"] = tail
     if planes_on:
@@ -296,16 +286,14 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
 
     def bn_sums(g, z, ctx, rows, act=0, dout=None):
         sums = pool.take(ctx.C)
-        L.check(lib.mt_bn_act_bwd(L.ptr(g), L.ptr(z), L.ptr(ctx.scale), L.ptr(ctx.shift), L.ptr(ctx.mean_invstd), None, None, None,
-                                  L.ptr(dout), L.ptr(sums), slots, rows, ctx.C, 1, act, L.stream_ptr()), "mt_bn_act_bwd")
+        L.mt.bn_act_bwd(g, z, ctx.scale, ctx.shift, ctx.mean_invstd, None, None, None, dout, sums, slots, rows, ctx.C, 1, act)
         return sums
 
     def bn_kabc(ctx, sums, gi, d, z, rows):
         """(d, z, rows): the gradient w.r.t. the BatchNorm's output and its input tensor (round 4's deterministic mode retook the sums
         from them; they are integer limbs now)."""
         kabc = _new(dev, 3, ctx.C)
-        L.check(lib.mt_bn_bwd_finalize(L.ptr(sums), slots, ctx.count, L.ptr(P[gi]), L.ptr(ctx.mean_invstd), L.ptr(kabc), L.ptr(grads[gi]),
-                                       L.ptr(grads[gi + 1]), ctx.C, tr, L.stream_ptr()), "mt_bn_bwd_finalize")
+        L.mt.bn_bwd_finalize(sums, slots, ctx.count, P[gi], ctx.mean_invstd, kabc, grads[gi], grads[gi + 1], ctx.C, tr)
         return kabc
 
     def unit_backward(rec, pi, g, sums, res_pre=None, res_post=None, pooled=None, res_half=False):
@@ -320,7 +308,7 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
             sums = bn_sums(p_dy, p_zmax, rec["bn"], N * p_Ho * p_Ho)      # sum du = sum dy, sum du xhat = sum dy xhat(arg-max)
             if rec["d_p"] is None:
                 g = _new(dev, M, co)
-                L.check(lib.mt_maxpool_bwd_arg(L.ptr(p_dy), L.ptr(p_arg), L.ptr(g), N, Hh, Hh, co, L.stream_ptr()), "mt_maxpool_bwd_arg")
+                L.mt.maxpool_bwd_arg(p_dy, p_arg, g, N, Hh, Hh, co)
         elif sums is None:
             sums = bn_sums(g, rec["z"], rec["bn"], M)
         kabc = bn_kabc(rec["bn"], sums, pi + 2, g, rec["z"], M)
@@ -331,11 +319,9 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
             # plane operands: dz = ka g + kb z + kc is evaluated ONCE, as planes, and feeds both gradient GEMMs
             dz_p = L.planes_empty(M, co, dev)
             if pooled is not None:
-                L.check(lib.mt_maxpool_bn_bwd_apply_planes(L.ptr(p_dy), L.ptr(p_arg), L.ptr(rec["z"]), L.ptr(kabc), L.ptr(dz_p), N, Hh, Hh, co,
-                                                           L.stream_ptr()), "mt_maxpool_bn_bwd_apply_planes")
+                L.mt.maxpool_bn_bwd_apply_planes(p_dy, p_arg, rec["z"], kabc, dz_p, N, Hh, Hh, co)
             else:
-                L.check(lib.mt_bn_bwd_apply_planes(L.ptr(g), L.ptr(rec["z"]), L.ptr(kabc), L.ptr(dz_p), M, co, L.stream_ptr()),
-                        "mt_bn_bwd_apply_planes")
+                L.mt.bn_bwd_apply_planes(g, rec["z"], kabc, dz_p, M, co)
             side.launch(lambda: L.gemm_planes(L.OP_TN, dz_p, rec["d_p"], co, ci, M, Cout=grads[pi + 1].view(co, ci), ldc=ci,
                                               epilogue=L.EPI_ATOMIC), reads=(dz_p, rec["d_p"]))
             L.gemm_planes(L.OP_NN, dz_p, rec["w_p"], M, ci, co, Cout=dd, ldc=ci)
@@ -353,10 +339,9 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
         du_in = _new(dev, M, ci)
 
         def dw_part(parts):
-            fn = lib.mt_dwconv_bwd_res2 if res_half else lib.mt_dwconv_bwd
-            L.check(fn(L.ptr(dd), L.ptr(dd), L.ptr(kid), L.ptr(w_dw), L.ptr(src.t), L.ptr(rec["sc"]), L.ptr(rec["sh"]),
-                       L.ptr(src.bn.mean_invstd) if has_bn else None, L.ptr(du_in), L.ptr(sums_in), slots, L.ptr(grads[pi]), N, Hh, Hh, ci,
-                       3, 1, parts, rec["eff"], L.ptr(res_pre), L.ptr(res_post), L.stream_ptr()), "mt_dwconv_bwd")
+            fn = L.mt.dwconv_bwd_res2 if res_half else L.mt.dwconv_bwd
+            fn(dd, dd, kid, w_dw, src.t, rec["sc"], rec["sh"], src.bn.mean_invstd if has_bn else None, du_in, sums_in, slots, grads[pi],
+               N, Hh, Hh, ci, 3, 1, parts, rec["eff"], res_pre, res_post)
         if not det:
             # data + weight gradient from one pass (effnet_backward.FUSED_DW; all of Xception's depthwise layers are 3x3 stride 1):
             # config 5 200.0 -> 193.5 ms.  Deterministic mode keeps the two kernels on two streams (the logged weight-gradient kernel)
@@ -413,8 +398,7 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
                 g, sums, pooled = None, None, (dy, brec["arg"], brec["zmax"], Ho)
             else:
                 du_last = torch.zeros(N * Hin * Hin, cout, dtype=torch.float32, device=dev)
-                L.check(lib.mt_maxpool_bwd(L.ptr(dy), L.ptr(last["z"]), L.ptr(last["bn"].scale), L.ptr(last["bn"].shift), L.ptr(du_last), N,
-                                           Hin, Hin, cout, L.stream_ptr()), "mt_maxpool_bwd")
+                L.mt.maxpool_bwd(dy, last["z"], last["bn"].scale, last["bn"].shift, du_last, N, Hin, Hin, cout)
                 g, sums = du_last, None
         else:
             g, sums, pooled = dy, None, None
@@ -449,10 +433,10 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
     n_side = N if (not side.enabled or det) else max(1, min(N, int(round(N * CONV2_WGRAD_SIDE))))
     side.launch(lambda: conv2_wgrad(0, n_side), reads=(dy, z1, z2, k2, dwp2, bn1.scale, bn1.shift))
     dz2 = _new(dev, M2, 64)
-    L.check(lib.mt_bn_bwd_apply(L.ptr(dy), L.ptr(z2), L.ptr(k2), L.ptr(dz2), M2, 64, L.stream_ptr()), "mt_bn_bwd_apply")
+    L.mt.bn_bwd_apply(dy, z2, k2, dz2, M2, 64)
     # data gradient of conv2 = "full" correlation of dz2 with the flipped kernel: im2col(dz2, pad 2) . W2flip^T
     wp2t = _new(dev, 32, 576)
-    L.check(lib.mt_conv_weight_pack(L.ptr(P[3]), L.ptr(wp2t), 64, 32, 3, 576, 1, L.stream_ptr()), "mt_conv_weight_pack")
+    L.mt.conv_weight_pack(P[3], wp2t, 64, 32, 3, 576, 1)
     da1 = _new(dev, M1, 32)
     L.gemm(L.OP_NT, dz2, wp2t, da1, M1, 32, 576, 576, 576, 32, prologue=L.PRO_IM2COL, conv=(H2, H2, 64, H1, H1, 3, 1, 2, NONE))
     du1 = _new(dev, M1, 32)
@@ -463,21 +447,19 @@ def xception_backward(model, params, saved, shape, training, dfeat, need_dparams
             raise NotImplementedError("gradient w.r.t. the input crops: mt_stem_conv_dgrad_valid takes crops of at most 512 columns")
         # the last operator of the walk: the transposed conv1, 32 -> 3 channels (csrc/stem_dgrad.hip)
         dx = _new(dev, N, H, W, 3)
-        L.check(lib.mt_stem_conv_dgrad_valid(L.ptr(du1), L.ptr(z1), L.ptr(k1), L.ptr(P[0]), L.ptr(dx), N, H, W, L.stream_ptr()),
-                "mt_stem_conv_dgrad_valid")
+        L.mt.stem_conv_dgrad_valid(du1, z1, k1, P[0], dx, N, H, W)
     if W <= 512:
-        L.check(lib.mt_stem_conv_wgrad_valid(L.ptr(du1), L.ptr(z1), L.ptr(k1), L.ptr(saved["x"]), 1 if saved["x"].dtype == torch.uint8 else 0,
-                                             L.ptr(grads[0]), N, H, W, L.stream_ptr()), "mt_stem_conv_wgrad_valid")
+        L.mt.stem_conv_wgrad_valid(du1, z1, k1, saved["x"], 1 if saved["x"].dtype == torch.uint8 else 0, grads[0], N, H, W)
     else:
         dwp1 = torch.zeros(32, 28, dtype=torch.float32, device=dev)
         L.gemm(L.OP_TN, du1, saved["x"], dwp1, 32, 28, M1, 32, 28, 28, prologue=L.PRO_BN_BWD, epilogue=L.EPI_ATOMIC, split_k=0, A2=z1,
                scale=k1[0], shift=k1[1], gate=k1[2], b_prologue=L.BPRO_IM2COL,
                conv=(H, W, 3, H1, H1, 3, 2, 0, NONE, 1 if saved["x"].dtype == torch.uint8 else 0))
-        L.check(lib.mt_conv_weight_unpack_grad(L.ptr(dwp1), L.ptr(grads[0]), 32, 3, 3, 28, L.stream_ptr()), "mt_conv_weight_unpack_grad")
+        L.mt.conv_weight_unpack_grad(dwp1, grads[0], 32, 3, 3, 28)
     if n_side < N:
         conv2_wgrad(n_side, N)
     side.wait()
-    L.check(lib.mt_conv_weight_unpack_grad(L.ptr(dwp2), L.ptr(grads[3]), 64, 32, 3, 288, L.stream_ptr()), "mt_conv_weight_unpack_grad")
+    L.mt.conv_weight_unpack_grad(dwp2, grads[3], 64, 32, 3, 288)
     if plan is not None:
         plan.extra["flat_grads"] = flat_grads
     L.grads_ready(model, P, flat_grads)
