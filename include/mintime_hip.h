@@ -791,6 +791,49 @@ int mt_avgpool_rows(const float* x, int64_t ldx, float* y, int64_t ldy, int N, i
 int mt_l2_normalize_rows(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int D, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Face crops for the embedder (csrc/face_crops.hip): what the reference does on the host, one face at a time, between the detector
+ * and InceptionResnetV1 -- the crop rule of predict.py:103-140 (= preprocessing/extract_crops.py:75-113) and preprocess_images
+ * (preprocessing/utils.py:32-34), torchvision Resize([128, 128]) of a PIL image = Pillow's Image.resize(BILINEAR), antialiased.
+ *
+ * mt_face_rects: boxes [T][4] fp32 (xmin, ymin, xmax, ymax; half-resolution frame coordinates) -> rects [T][4] int32
+ *   (x0, y0, w, h) in the H x W frame, valid [T] bytes.  One thread per face, integers only:
+ *     every coordinate is doubled and truncated toward zero (it may be negative); bw, bh = the box's width and height;
+ *     padding pw = floor(bw / 3), ph = floor(bh / 3) (floor, also of a negative);
+ *     the padded spans sw = (xmax + pw) - max(xmin - pw, 0), sh likewise; the LONGER span's padding is reduced by
+ *     trunc((longer - shorter) / 2), which squares the window while it is inside the frame (on a tie pw takes the zero);
+ *     window = rows max(ymin - ph, 0) .. ymax + ph, columns max(xmin - pw, 0) .. xmax + pw, the far ends cut at H and W;
+ *     if that window (cut by an edge) is not square, the longer side loses d = trunc(|h - w| / 2) at BOTH ends when d > 0; when
+ *     d == 0 (sides one apart) a taller window drops its FIRST row, a wider one its LAST column.  The result may stay one off square.
+ *   valid = 0, rect = (0, 0, 0, 0) and *err += 1 (sticky device int32 counter, NULL allowed) when the window is empty, when a far
+ *   end is negative (a Python slice would wrap around), when a side is longer than 4096, when frame_index[t] is outside [0, N), or
+ *   when a coordinate is not finite or beyond 2^29.  H, W >= 1, N >= 1, T >= 0.
+ *
+ * mt_crop_resize_u8: T source windows of any size -> out [T][OH][OW][3] uint8, one launch, no host read.  The source is either
+ *   frames  src = [N][H][W][3] uint8 with rects / frame_index / valid as mt_face_rects leaves them (crops == NULL), or
+ *   packed  src = a byte buffer of src_bytes bytes, crops [T][4] int64 = (byte offset, row pitch in bytes, w, h) of ready RGB crops.
+ *   A face whose entry is not valid, or does not lie inside the source, or has a side outside 1..4096 comes out all zeros; the
+ *   latter two also set bit 0 of err[1] (err = device int32 [2] or NULL; err[0] is mt_face_rects' counter).
+ *   Per axis, in IEEE double without contraction (in = window side, out = output side):
+ *     scale = in / out, fs = max(scale, 1), support = fs, ksize = 2 ceil(support) + 1; for output index i:
+ *     center = (i + 0.5) scale, first = max((int)(center - support + 0.5), 0), n = min((int)(center + support + 0.5), in) - first,
+ *     w_j = max(1 - |(j + first - center + 0.5) / fs|, 0) for j < n, summed in index order, each divided by the sum,
+ *     k_j = (int)(w_j 2^22 + 0.5);  a pass is  clip((2^21 + sum_j pixel_j k_j) >> 22, 0, 255)  in int32.
+ *     (Pillow's C multiplies by 1.0 / fs where this divides by fs; the k_j of the two forms are equal wherever they were compared:
+ *     every in of 1..4096 at out = 1, 2, 3, 96, 128, 160, 256.)
+ *   The horizontal pass runs first into uint8, the vertical pass over that -- except, as Image.resize itself does, for a window more
+ *   than 100 times as tall as wide with OH < h, which is resized vertically first.  1 <= OH, OW <= 256, T <= 65535 (grid.y), else
+ *   MT_ERR_UNSUPPORTED before anything is launched.  max_w: an upper bound of the window widths (<= 4096) known to the host; it
+ *   sizes the x coefficient table in LDS, never the result (a window whose table would not fit counts as outside the source).  A
+ *   face's bytes do not depend on the batch.  Grid = (8 bands of output rows, T); a block walks its band in sub-bands whose
+ *   horizontal-pass rows fit its LDS tile.
+ * ------------------------------------------------------------------------------------------------ */
+int mt_face_rects(const float* boxes, const int* frame_index, int T, int N, int H, int W, int* rects, unsigned char* valid, int* err,
+                  void* stream);
+int mt_crop_resize_u8(const unsigned char* src, int64_t src_bytes, int N, int H, int W, const int* rects, const int* frame_index,
+                      const unsigned char* valid, const int64_t* crops, int T, int max_w, int OH, int OW, unsigned char* out,
+                      int* err, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Launch plans (the caller side of the step: reference train.py:332-378, the Python loop that issues every op).
  * A plan holds the SEQUENCE of entry-point calls of one phase (EfficientNet forward, TimeSformer forward, TimeSformer backward,
  * EfficientNet backward) so that the host issues a phase with one call instead of hundreds through its FFI.

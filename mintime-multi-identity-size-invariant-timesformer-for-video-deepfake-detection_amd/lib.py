@@ -169,6 +169,8 @@ LAUNCHES = {
     "mt_maxpool2d_fwd": [f32p, i64, f32p, i64] + [C.c_int] * 7 + [C.c_void_p],
     "mt_avgpool_rows": [f32p, i64, f32p, i64, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "mt_l2_normalize_rows": [f32p, i64, f32p, i64, i64, C.c_int, C.c_float, C.c_void_p],
+    "mt_face_rects": [f32p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4,
+    "mt_crop_resize_u8": [C.c_void_p, i64] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 3,
     "mt_memset_async": [C.c_void_p, C.c_int, i64, C.c_void_p],
     "mt_copy_async": [C.c_void_p, C.c_void_p, i64, C.c_void_p],
 }
