@@ -93,8 +93,14 @@ typedef struct {
   int split_k;                      /* TN: number of K splits; <= 0 picks one that fills the chip        */
   const float* A2;                  /* BN_BWD prologue: second source, same layout as A                  */
   int b_prologue; const float* b_scale; const float* b_shift; const float* b_gate; int b_hw;
-  int conv_H, conv_W, conv_C, conv_Ho, conv_Wo, conv_k, conv_stride, conv_pad, conv_act;   /* im2col prologues */
-  int conv_src_u8;                  /* im2col source image is uint8 (raw crops, 3 channels) instead of fp32      */
+  /* im2col prologues: the gathered operand (A of NT with MT_PRO_IM2COL and STORE / STATS; B of TN with MT_BPRO_IM2COL, BN_BWD on A
+     and ATOMIC) is a dense NHWC image [n][conv_H][conv_W][conv_C] without a leading dimension.  Its virtual matrix has one row per
+     output pixel (n, oh, ow), oh < conv_Ho, ow < conv_Wo (taken as given: a window may hang over the bottom / right edge), and one
+     column per (kh, kw, ci); it is exactly zero where the tap lies outside the image (the padding passes through neither the affine
+     scale / shift, resp. b_scale / b_shift, nor the activation) and in the columns from k*k*C up to the contraction width (K of NT,
+     N of TN), which must be at least k*k*C.  conv_pad is the one leading pad of both axes; conv_act: 0 none, 2 relu. */
+  int conv_H, conv_W, conv_C, conv_Ho, conv_Wo, conv_k, conv_stride, conv_pad, conv_act;
+  int conv_src_u8;                  /* im2col source image is uint8 (raw crops, conv_C % 4 != 0) instead of fp32  */
   float* col_sum;                   /* GEGLU_BWD: optional [2*n_half] column sums of the stored gradient (= d bias of the
                                        Linear that produced the pre-activations), atomically accumulated; caller zero-fills */
   const void* b_planes;             /* NT only, optional: B pre-split by mt_split_planes (three bf16 planes, each [N][K] with B's

@@ -87,8 +87,22 @@ extern "C" void mt_debug_split_k(int K, int tiles, int split_k, int auto_target,
   out4[0] = r.k_chunk; out4[1] = r.ranges; out4[2] = r.grid_y; out4[3] = r.xcd_k;
 }
 
+// the tile of a register-staged launch: pick_cfg's, but for the weight gradient of a dense convolution with <= 64 output channels and
+// 192 < columns <= 288 the one-tile configuration
+static int launch_cfg(int op, int M, int N, int prologue, int b_prologue, int epilogue) {
+  const int cfg = pick_cfg(op, M, N, prologue, epilogue);
+  if (op == MT_OP_TN && b_prologue == MT_BPRO_IM2COL && epilogue == MT_EPI_ATOMIC && M <= 64 && N > 192 && N <= 288)
+    return det_enabled() ? CFG_WG64 : CFG_WG64K;   // (deterministic mode writes per-split slabs: one writer per tile)
+  return cfg;
+}
+// test aid like the two above: the tile mt_gemm's register-staged kernels would run that call on
+extern "C" void mt_debug_gemm_tile(int op, int M, int N, int prologue, int b_prologue, int epilogue, int* out2) {
+  const Cfg c = kCfg[launch_cfg(op, M, N, prologue, b_prologue, epilogue)];
+  out2[0] = c.bm; out2[1] = c.bn;
+}
+
 static int gemm_impl(const mt_gemm_desc* d, void* stream) {
-  if (!d || !d->A || !d->B || !d->C) return fail(MT_ERR_ARG, "mt_gemm: null pointer");
+  if (!d ||!d->A || !d->B || !d->C) return fail(MT_ERR_ARG, "mt_gemm: null pointer");
   if (d->M <= 0 || d->N <= 0 || d->K <= 0) return fail(MT_ERR_ARG, "mt_gemm: bad shape %d %d %d", d->M, d->N, d->K);
   if ((d->lda & 3) || (d->ldb & 3)) return fail(MT_ERR_ARG, "mt_gemm: lda/ldb must be multiples of 4 floats");
   const bool u8_src = d->conv_src_u8 != 0;
@@ -133,6 +147,12 @@ static int gemm_impl(const mt_gemm_desc* d, void* stream) {
   if (d->prologue == MT_PRO_IM2COL || d->b_prologue == MT_BPRO_IM2COL) {
     if (d->conv_k <= 0 || d->conv_stride <= 0 || d->conv_C <= 0 || d->conv_Ho <= 0 || d->conv_Wo <= 0)
       return fail(MT_ERR_ARG, "mt_gemm: im2col prologue needs the conv_* geometry");
+    if (d->conv_H <= 0 || d->conv_W <= 0) return fail(MT_ERR_ARG, "mt_gemm: im2col image of %d x %d", d->conv_H, d->conv_W);
+    // the gathered operand's contraction width (A: K of NT; B: N of TN) holds all k*k*C columns of the virtual matrix
+    const int64_t taps = (int64_t)d->conv_k * d->conv_k * d->conv_C;
+    if ((d->prologue == MT_PRO_IM2COL && d->K < taps) || (d->b_prologue == MT_BPRO_IM2COL && d->N < taps))
+      return fail(MT_ERR_ARG, "mt_gemm: im2col needs %lld columns (k*k*C), the call gives %d", (long long)taps,
+                  d->prologue == MT_PRO_IM2COL ? d->K : d->N);
     if (d->conv_src_u8 && (d->conv_C & 3) == 0) return fail(MT_ERR_UNSUPPORTED, "mt_gemm: uint8 im2col source needs C %% 4 != 0 (3-channel crops)");
     if ((d->scale == nullptr) != (d->shift == nullptr) || (d->b_scale == nullptr) != (d->b_shift == nullptr))
       return fail(MT_ERR_ARG, "mt_gemm: im2col affine needs both scale and shift");
@@ -158,9 +178,7 @@ static int gemm_impl(const mt_gemm_desc* d, void* stream) {
     rc = try_launch_dma(d, a, s);
     if (rc <= 0) return rc;
   }
-  int cfg = pick_cfg(d->op, d->M, d->N, d->prologue, d->epilogue);
-  if (d->op == MT_OP_TN && d->b_prologue == MT_BPRO_IM2COL && d->epilogue == MT_EPI_ATOMIC && d->M <= 64 && d->N > 192 && d->N <= 288)
-    cfg = det_enabled() ? CFG_WG64 : CFG_WG64K;   // (deterministic mode writes per-split slabs: one writer per tile)
+  const int cfg = launch_cfg(d->op, d->M, d->N, d->prologue, d->b_prologue, d->epilogue);
   const TileGrid tg = tile_grid(d->M, d->N, kCfg[cfg].bm, kCfg[cfg].bn, (int64_t)kCfg[cfg].bn * d->K * 4);
   dim3 grid(tg.grid_x, 1, 1);
   a.group_n = tg.group_n;

@@ -30,7 +30,6 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
     N, H, W = shape
     blocks = model._blocks
     P = list(params)
-    grads, flat_grads = L.zero_grads(list(params), with_flat=True)
     # parameter index map (same order as effnet_engine.param_list)
     pos = 3
     bidx = []
@@ -62,6 +61,18 @@ def effnet_backward(model, params, saved, shape, training, dfeat, need_dx, need_
         need_below = [True] * len(blocks)
         if W > 512:
             raise NotImplementedError("gradient w.r.t. the input crops: mt_stem_conv_dgrad takes crops of at most 512 columns")
+    # mt_dwconv_bwd takes stride-2 layers over even sizes only (image sizes whose halvings stay even down to the last stride-2 block:
+    # multiples of 32).  The forward has no such limit; say so here, before anything is allocated or launched (the gradient buffer
+    # below included), not from the middle of the walk.  A block of the walk calls it for its own depthwise weight or for anything
+    # trainable underneath (need_du_in in the loop below)
+    def runs_dw(bi):
+        s, ix = blocks[bi].spec, bidx[bi]
+        return need[ix["d"]] or need_below[bi] or (s.has_expand and any(need[ix["e"]:ix["e"] + 3]))
+    odd = [b.spec.idx for bi, b in enumerate(blocks) if bi >= lowest and b.spec.s == 2 and b.spec.hin % 2 and runs_dw(bi)]
+    if odd:
+        raise NotImplementedError(f"EfficientNet backward for {H} x {W} crops: the stride-2 depthwise layers of blocks {odd} see odd "
+                                  "sizes, which mt_dwconv_bwd does not take")
+    grads, flat_grads = L.zero_grads(list(params), with_flat=True)
     dx = None
     run = {"blocks_run": 0, "wgrad_launches": 0, "stem_run": False}
     total_c = arch.STEM_COUT + arch.HEAD_COUT + sum((b.spec.cexp if b.spec.has_expand else 0) + b.spec.cexp + b.spec.cout

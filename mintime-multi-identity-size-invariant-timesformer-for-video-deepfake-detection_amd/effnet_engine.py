@@ -168,6 +168,15 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
     lib = L.get()
     dev = x_nhwc.device
     N, H, W, _ = x_nhwc.shape
+    # every block's row count below comes from the model's specs (arch.effnet_b0_blocks(image_size): one hin / hout per block), so the
+    # walk serves square crops of the model's image_size and nothing else: any other shape would read past the stem's output.  Refused
+    # here, before anything is allocated or launched
+    if H != model.image_size or W != model.image_size:
+        raise ValueError(f"EfficientNet engine: crops of H = {H} by W = {W}, the model was built for "
+                         f"{model.image_size} x {model.image_size} (one size per axis in every MBConv spec)")
+    # the stem's leading TF-SAME pad (utils.py:248-276: the smaller half of the total goes in front): 0 for an even size, 1 for an odd
+    Hc, Wc = (H + 1) // 2, (W + 1) // 2
+    stem_pad = max((Hc - 1) * 2 + 3 - H, 0) // 2
     blocks = model._blocks
     total_c = arch.STEM_COUT + arch.HEAD_COUT + sum((b.spec.cexp if b.spec.has_expand else 0) + b.spec.cexp + b.spec.cout
                                                     for b in blocks)
@@ -183,18 +192,17 @@ def effnet_forward(model, x_nhwc, params, training, save, want_blocks=False, pla
 
     # ---- stem
     w_stem, g0, b0 = next(it), next(it), next(it)
-    Hc, Wc = (H + 1) // 2, (W + 1) // 2
     bn = _BNCtx(dev, arch.STEM_COUT, training, pool)
     z = _new(dev, N * Hc * Wc, arch.STEM_COUT)
     # stem: streaming MFMA kernel (stem_fwd.hip; uint8 crops converted on the fly, BatchNorm statistics in the same pass).  The
     # im2col-prologue GEMM it replaced (K = 27 taps padded to 28) stays the path for crops wider than the kernel's LDS row tile.
-    if W <= 512 and H == W:
+    if W <= 512:
         L.mt.stem_conv_fwd(x_nhwc, 1 if x_nhwc.dtype == torch.uint8 else 0, w_stem, z, bn.stats, slots, N, H, W)
     else:
         wp = _new(dev, arch.STEM_COUT, 28)
         L.mt.conv_weight_pack(w_stem, wp, arch.STEM_COUT, 3, 3, 28, 0)
         L.gemm(L.OP_NT, x_nhwc, wp, z, N * Hc * Wc, arch.STEM_COUT, 28, 28, 28, arch.STEM_COUT, prologue=L.PRO_IM2COL, epilogue=epi,
-               stats=bn.stats, stats_slots=slots, conv=(H, W, 3, Hc, Wc, 3, 2, 0, 0, 1 if x_nhwc.dtype == torch.uint8 else 0))
+               stats=bn.stats, stats_slots=slots, conv=(H, W, 3, Hc, Wc, 3, 2, stem_pad, 0, 1 if x_nhwc.dtype == torch.uint8 else 0))
     _finalize(model._bn0, bn, N * Hc * Wc, training, g0, b0, slots)
     if save:
         saved["stem"] = dict(x=x_nhwc, z=z, bn=bn)

@@ -5,20 +5,27 @@ A Case names one mt_gemm call.  build(case) draws its operands ON THE CPU as the
 a non-zero 16-byte aligned offset, of a wider noise-filled tensor (leading dimension = width + 8 floats), every output is such a slice
 of a tensor whose other columns hold SLICE_CANARY.  reference(case) evaluates tests/gemm_ref.py on those tensors in fp64, once per
 case (cached, never modified).  Cases with a summed output (STATS, the ACT_BWD sums, col_sum, SE_RED) draw operands with a positive
-mean, so that no reported sum cancels (test_gemm_ref_host.py asserts |S| >= 0.05 sum|v_i| for every column of every case)."""
+mean, so that no reported sum cancels (test_gemm_ref_host.py asserts |S| >= 0.05 sum|v_i| for every column of every case).
+
+The im2col forms (Case.conv) gather one operand from an image, which has no leading dimension: it is a dense NHWC tensor, fp32 or uint8,
+at element IMG_OFF of a longer noise-filled allocation (Built.flat).  The packed weights of the forward cases are ordinary pitched slices
+whose columns from k k C on hold the same noise as the rest, so a kernel that multiplies past k k C shows; the weight gradients start
+from CANARY and must leave it, exactly, in those columns.  test_gemm_ref_host.py shows that the case list tells six planted mistakes of
+a gather from the reference."""
 import functools
 from dataclasses import dataclass, field, replace
 
 import torch
 
 from . import gemm_ref as R
-from .gemm_ref import (OP_NT, OP_NN, OP_TN, PRO_NONE, PRO_BN_SWISH_GATE, PRO_BN_BWD, BPRO_NONE, BPRO_BN_SWISH_GATE, EPI_STORE,
-                       EPI_BIAS_RES, EPI_GEGLU, EPI_STATS, EPI_ATOMIC, EPI_GEGLU_BWD, EPI_ACCUM, EPI_SE_RED, EPI_ACT_BWD)
+from .gemm_ref import (OP_NT, OP_NN, OP_TN, PRO_NONE, PRO_BN_SWISH_GATE, PRO_BN_BWD, PRO_IM2COL, BPRO_NONE, BPRO_BN_SWISH_GATE,
+                       BPRO_IM2COL, ACT_NONE, ACT_RELU, EPI_STORE, EPI_BIAS_RES, EPI_GEGLU, EPI_STATS, EPI_ATOMIC, EPI_GEGLU_BWD, EPI_ACCUM, EPI_SE_RED, EPI_ACT_BWD)
 
 F64 = torch.float64
 CANARY = 7.0            # initial value of accumulated outputs (the reference adds it)
 SLICE_CANARY = 5.0      # the columns of an output's wider tensor that the call must not touch
 PAD, OFF = 8, 4         # every pitched tensor: leading dimension = width + PAD, slice at column OFF (both multiples of 4 floats)
+IMG_OFF = 16            # a gathered image starts at this element of its allocation (16 bytes of uint8, 64 of fp32)
 HIGH_BOUND = 3.1 * 2.0 ** -16          # include/mintime_hip.h, MT_PRECISION_HIGH: |error| <= 3.1 * 2^-16 * sum|a||b|
 
 # Gates.  Every figure is max|got - ref| / max|ref| over ONE section (sections()); gate = 2 x the worst case measured on an MI355X over
@@ -30,9 +37,18 @@ HIGH_BOUND = 3.1 * 2.0 ** -16          # include/mintime_hip.h, MT_PRECISION_HIG
 TOL = {
     "store": 1e-6,          # 4.516e-7 (first row tile, dma3 NT store+bias 64x64x128); yardstick 4.069e-7
     "l2.store": 7e-6,       # 3.030e-6 (interior, l2 NT store 2116x132x4100: 4100 products per element); yardstick 7.956e-7
+    # (the im2col forward cases up to K 196 reach 6.268e-7 -- last row tile, cfg3 generic 12x15x4 k7, NT 96x24x196 -- yardstick 5.765e-7:
+    #  stored results do not vary from run to run, and the key stays as it is)
+    "im2col.store": 3e-6,   # 1.132e-6 (first row tile, cfg3 im2col granule 5x7x64 k3 p2, NT 126x32x576: 576 products per element on the fp32 pipe; the one im2col forward case that does not fit "store"); yardstick 6.588e-7
     "atomic": 1e-6,         # 4.541e-7 (first row tile, bpro b_hw49 split 0, TN 40x72x147); yardstick 4.541e-7
+    # (the im2col weight gradients reach 6.931e-7 -- first row tile, one-tile 9x11x8 k5 split 1, TN 32x200x297, a single K range: the
+    #  same in every run -- yardstick 6.931e-7: the fp32 rounding of the BN_BWD operand, not of the summation; the key stays as it is.
+    #  The split_k 3 and auto cases add their K ranges in the order they finish: over six runs 8 of their 74 sections moved at all, by
+    #  1.9e-8 at the most -- one-tile 7x9x32 k3 split 3 -- and none passed 6.931e-7: the margin left under the gate is 16 x that spread)
     "fused": 2e-6,          # 5.372e-7 (worst image, dma_pro3 act_bwd NN 4200x72x96; twice that is 1.07e-6); yardstick 5.372e-7
     "sums": 4e-7,           # 1.620e-7 (sum du xhat, inner columns, act_bwd e_hw1 NN 133x136x36, slots 8); yardstick 1.375e-7
+    # (the im2col STATS cases reach 1.886e-7 -- sum of squares, first column tile, cfg0 granule 5x7x64 k3 p2, NT 126x32x576 -- yardstick
+    #  1.281e-7: fp64 slots, the same in every run; the key stays as it is)
     "split.store": 2e-6,    # 6.667e-7 (first column tile, S_BIG NN store 1032x264x520); yardstick 7.193e-7
     "split.atomic": 2e-6,   # 5.182e-7 (last row tile, bn_bwd TN atomic 136x248x8200); yardstick 1.633e-7
     "split.fused": 2e-6,    # 5.167e-7 (da last column tile, split NN geglu_bwd 1032x256x520); yardstick 3.333e-7
@@ -75,6 +91,13 @@ class Case:
     tier: str = "highest"
     long_k: bool = False            # thousands of fp32 products per element on the fp32 pipe: its own gate ("l2.")
     seed: int = 0
+    conv: tuple = ()                # im2col forms: (H, W, C, Ho, Wo, k, stride, pad, act) of the gathered operand (A of NT, B of TN)
+    src: str = "f32"                # im2col forms: the image's kind, "f32" or "u8"
+    affine: bool = False            # im2col forms: the gather carries a per-channel scale / shift
+
+    @property
+    def taps(self):                 # k k C: the im2col matrix's columns that hold image data
+        return self.conv[5] * self.conv[5] * self.conv[2]
 
     @property
     def summed(self):
@@ -93,7 +116,9 @@ class Case:
         """TOL key of C."""
         base = ("atomic" if self.epi == EPI_ATOMIC else
                 "fused" if self.epi in (EPI_GEGLU, EPI_GEGLU_BWD, EPI_SE_RED, EPI_ACT_BWD) or self.pro == PRO_BN_SWISH_GATE or
-                self.bpro != BPRO_NONE else "store")
+                self.bpro not in (BPRO_NONE, BPRO_IM2COL) else "store")
+        if self.pro == PRO_IM2COL and self.K >= 512:       # hundreds of fp32 products per element: the im2col forward's own gate
+            return "im2col." + base
         return self.prefix + base
 
     @property
@@ -110,10 +135,15 @@ class Built:
     cols: dict = field(default_factory=dict)     # name -> width of the slice (2-D tensors only)
     outputs: tuple = ()                          # names of the tensors the call writes
     kw: dict = field(default_factory=dict)       # keyword arguments of gemm(); tensors by NAME
+    flat: dict = field(default_factory=dict)     # name -> (first element, elements) of a dense operand inside its 1-D allocation (im2col images)
 
     def views(self, tensors):
         """name -> the operand as the call receives it, from name -> tensor laid out like self.wide (any device / dtype)."""
-        return {k: (t if k not in self.cols else t[:, OFF:OFF + self.cols[k]]) for k, t in tensors.items()}
+        def view(k, t):
+            if k in self.flat:
+                return t[self.flat[k][0]:self.flat[k][0] + self.flat[k][1]]
+            return t if k not in self.cols else t[:, OFF:OFF + self.cols[k]]
+        return {k: view(k, t) for k, t in tensors.items()}
 
     def call(self, fn, v, **over):
         """fn(op, A, B, C, M, N, K, lda, ldb, ldc, **kw) with the tensors of `v` (from views()); `over` replaces keyword arguments."""
@@ -125,7 +155,8 @@ class Built:
             else:
                 kw[k] = v.get(val) if isinstance(val, str) else val
         kw.update(over)
-        ld = lambda n: self.wide[n].shape[1]
+        # a gathered image has no leading dimension: the engines pass the virtual matrix's width
+        ld = lambda n: self.wide[n].shape[1] if n not in self.flat else (c.K if n == "A" else c.N)
         return fn(c.op, v["A"], v["B"], v["C"], c.M, c.N, c.K, ld("A"), ld("B"), ld("C"), **kw)
 
 
@@ -137,7 +168,25 @@ def build(case):
     c = case
     g = torch.Generator().manual_seed(1234 + c.seed)
     b = Built(c)
-    pos = c.summed
+    pos = c.summed or c.pro == PRO_IM2COL            # a convolution's forward is drawn once for STORE and STATS
+
+    def image(name, rows):
+        """The gathered operand as the engines pass it: a dense NHWC image (fp32 around 1, or uint8 over the whole range) at element
+        IMG_OFF of a longer noise-filled 1-D allocation, and the optional per-channel affine (the shift mostly positive, so that
+        act(shift) != 0 where a kernel lets the padding through the affine)."""
+        H, W, C, Ho, Wo = c.conv[:5]
+        assert rows % (Ho * Wo) == 0
+        numel = rows // (Ho * Wo) * H * W * C
+        if c.src == "u8":
+            b.wide[name] = torch.randint(0, 256, (IMG_OFF + numel + 64,), generator=g, dtype=torch.uint8)
+        else:
+            b.wide[name] = randn(IMG_OFF + numel + 64, mean=1.0, std=0.5)
+        b.flat[name] = (IMG_OFF, numel)
+        pre = "" if name == "A" else "b_"
+        if c.affine:
+            b.wide[pre + "scale"], b.wide[pre + "shift"] = rand(C) + 0.5, randn(C, mean=0.5, std=0.5)
+            b.kw.update({pre + "scale": pre + "scale", pre + "shift": pre + "shift"})
+        b.kw["conv"] = c.conv + (1 if c.src == "u8" else 0,)
 
     def randn(*shape, mean=0.0, std=1.0):
         return torch.randn(*shape, generator=g) * std + mean
@@ -171,6 +220,9 @@ def build(case):
         pitched("A2", a_rows, a_cols)
         b.wide["scale"], b.wide["shift"], b.wide["gate"] = rand(ch) + 0.5, randn(ch, std=0.1), rand(ch) * 0.5 + 0.25
         b.kw.update(prologue=c.pro, scale="scale", shift="shift", gate="gate", A2="A2")
+    elif c.pro == PRO_IM2COL:
+        image("A", M)
+        b.kw.update(prologue=c.pro)
     else:
         pitched("A", a_rows, a_cols, mean=am, std=0.5 if pos else 1.0)
     # ---- B: NT [N, K], NN / TN [K, N] (rows through b_map)
@@ -182,6 +234,9 @@ def build(case):
         b.wide["b_scale"], b.wide["b_shift"] = rand(N) + 0.5, rand(N) + 0.5
         b.wide["b_gate"] = torch.sigmoid(randn((K - 1) // c.b_hw + 1, N))
         b.kw.update(b_prologue=c.bpro, b_scale="b_scale", b_shift="b_shift", b_gate="b_gate", b_hw=c.b_hw)
+    elif c.bpro == BPRO_IM2COL:
+        image("B", K)
+        b.kw.update(b_prologue=c.bpro)
     else:
         pitched("B", _mapped_rows(c.b_map, K), N, mean=wm * inv, std=ws * inv)
     # ---- C and the epilogue's extras
@@ -497,10 +552,86 @@ def extra_cases():
             Case("split NN geglu_bwd", OP_NN, 1032, 256, 520, epi=EPI_GEGLU_BWD, n_half=256, tile=(128, 64), **s)]
 
 
+# ---- the im2col forms ---------------------------------------------------------------------------------------------------------------
+
+def _pad4(n):
+    return (n + 3) // 4 * 4
+
+
+# A side (NT): (kind, n, H, W, C, k, s, p, Ho, Wo, Cout, affine, act, sources).  The smallest shapes that reach each edge:
+IM2COL_A = [
+    # M 627: ragged last row tile at 64, 128 and 256; 72 columns: ragged at 32, 64 and 128; act(shift) != 0 at the padding
+    ("granule", 3, 11, 19, 8, 3, 1, 1, 11, 19, 72, True, ACT_RELU, ("f32",)),
+    ("granule", 2, 13, 18, 4, 5, 2, 2, 7, 9, 40, True, ACT_NONE, ("f32",)),          # 25-bit tap mask, stride 2 on an odd H
+    ("granule", 2, 5, 7, 64, 3, 1, 2, 7, 9, 32, False, ACT_NONE, ("f32",)),          # K 576: the "full" correlation of a data gradient
+    ("granule", 2, 4, 6, 4, 3, 1, 3, 8, 10, 16, True, ACT_RELU, ("f32",)),           # padding >= k: whole windows outside the image
+    ("granule", 3, 9, 12, 64, 1, 2, 0, 5, 6, 136, True, ACT_RELU, ("f32",)),         # strided 1 x 1 skip convolution
+    ("generic", 2, 10, 14, 3, 3, 2, 0, 5, 7, 32, False, ACT_NONE, ("f32", "u8")),    # Ho = ceil(H / 2) at pad 0: the SAME overhang; K 28
+    ("generic", 2, 9, 13, 3, 3, 2, 1, 5, 7, 32, False, ACT_NONE, ("f32", "u8")),     # odd sizes, leading pad 1
+    ("generic", 2, 9, 13, 3, 3, 2, 0, 4, 6, 32, False, ACT_NONE, ("f32", "u8")),     # valid padding
+    ("generic", 2, 12, 15, 4, 7, 2, 3, 6, 8, 24, True, ACT_RELU, ("f32",)),          # k k = 49 > 32 leaves the granule form; K 196
+]
+
+
+def _geo(H, W, C, k, s, p, Ho, Wo):
+    return f"{H}x{W}x{C} k{k} s{s} p{p} -> {Ho}x{Wo}"
+
+
+def im2col_a_cases(cfg):
+    """MT_PRO_IM2COL (NT) with EPI_STORE and EPI_STATS on the tile MT_FORCE_CFG = cfg forces; granule form (fp32, C % 4 == 0,
+    k k <= 32) and generic form (3 channels, uint8, k k > 32)."""
+    bm, bn = CFG_TILES[cfg]
+    cs = []
+    for i, (kind, n, H, W, C, k, s, p, Ho, Wo, Cout, aff, act, srcs) in enumerate(IM2COL_A):
+        for src in srcs:
+            for e in (EPI_STORE, EPI_STATS):
+                cs.append(Case(f"cfg{cfg} im2col {kind} {src} {_geo(H, W, C, k, s, p, Ho, Wo)} {'stats' if e == EPI_STATS else 'store'}",
+                               OP_NT, n * Ho * Wo, Cout, _pad4(k * k * C), pro=PRO_IM2COL, epi=e, conv=(H, W, C, Ho, Wo, k, s, p, act),
+                               src=src, affine=aff, tile=(bm, bn), env=(("MT_FORCE_CFG", str(cfg)),), seed=60 + i))
+    return cs
+
+
+# B side (TN, BN_BWD + ATOMIC onto CANARY): (group, H, W, C, k, s, p, Ho, Wo, Cout, affine, act, sources, tile); Ho and Wo are given, as
+# on the A side (10 x 14 at pad 0 -> 5 x 7 is the SAME overhang).  Three images each; Ho Wo is odd wherever the geometry leaves the
+# choice (3 x 16 and the valid stem geometry are 48 and 24 pixels), so that an image boundary falls inside a 16-pixel k-step.  The tile
+# is the one gemm.hip picks: 128 x 128 for 72 columns, 256 x 32 for 28, the one-tile 64 x 288 for Cout <= 64 and 192 < columns <= 288,
+# 128 x 64 for 288 columns at Cout 68 and for 192 columns (test_gemm_ref_host.py asks the library).
+IM2COL_B = [
+    ("granule", 5, 7, 8, 3, 1, 1, 5, 7, 72, True, ACT_RELU, ("f32",), (128, 128)),          # Wo 7: below the k-step
+    ("granule", 3, 16, 8, 3, 1, 1, 3, 16, 72, True, ACT_RELU, ("f32",), (128, 128)),        # Wo 16: the k-step
+    ("granule", 3, 17, 8, 3, 1, 1, 3, 17, 72, True, ACT_RELU, ("f32",), (128, 128)),        # Wo 17: just above it
+    ("granule", 3, 37, 8, 3, 1, 1, 3, 37, 72, True, ACT_RELU, ("f32",), (128, 128)),        # Wo 37: more than twice it
+    ("granule", 9, 13, 8, 3, 2, 1, 5, 7, 72, True, ACT_RELU, ("f32",), (128, 128)),         # stride 2, Wo 7
+    ("one-tile", 7, 9, 32, 3, 1, 0, 5, 7, 64, True, ACT_RELU, ("f32",), (64, 288)),         # 288 columns, Cout 64
+    ("one-tile", 9, 11, 8, 5, 1, 2, 9, 11, 32, True, ACT_NONE, ("f32",), (64, 288)),        # 200 columns, Cout 32
+    ("ordinary", 7, 9, 32, 3, 1, 0, 5, 7, 68, True, ACT_RELU, ("f32",), (128, 64)),         # Cout 68: just outside the one-tile configuration
+    ("ordinary", 9, 13, 192, 1, 2, 0, 5, 7, 64, True, ACT_RELU, ("f32",), (128, 64)),       # 192 columns: just outside it (strided 1 x 1)
+    ("generic", 10, 14, 3, 3, 2, 0, 5, 7, 32, False, ACT_NONE, ("f32", "u8"), (256, 32)),
+    ("generic", 9, 13, 3, 3, 2, 1, 5, 7, 32, False, ACT_NONE, ("f32", "u8"), (256, 32)),
+    ("generic", 9, 13, 3, 3, 2, 0, 4, 6, 32, False, ACT_NONE, ("f32", "u8"), (256, 32)),
+    ("generic", 13, 17, 4, 7, 2, 3, 7, 9, 24, True, ACT_RELU, ("f32",), (64, 288)),         # k k = 49: the per-element gather on the one tile
+    ("generic", 13, 17, 4, 7, 2, 3, 7, 9, 72, True, ACT_RELU, ("f32",), (128, 128)),        # ... and on the ordinary path
+]
+IM2COL_B_IMAGES = 3
+
+
+def im2col_b_cases():
+    """MT_BPRO_IM2COL (TN, BN_BWD prologue on A, ATOMIC): the weight gradients, each at split_k 1, 3 and 0 (auto)."""
+    cs = []
+    for i, (group, H, W, C, k, s, p, Ho, Wo, Cout, aff, act, srcs, tile) in enumerate(IM2COL_B):
+        for src in srcs:
+            for sk in (1, 3, 0):
+                cs.append(Case(f"im2col wgrad {group} {src} {_geo(H, W, C, k, s, p, Ho, Wo)} Cout {Cout} split {sk}", OP_TN, Cout,
+                               _pad4(k * k * C), IM2COL_B_IMAGES * Ho * Wo, pro=PRO_BN_BWD, bpro=BPRO_IM2COL, epi=EPI_ATOMIC, split_k=sk,
+                               conv=(H, W, C, Ho, Wo, k, s, p, act), src=src, affine=aff, tile=tile, seed=80 + i))
+    return cs
+
+
 def all_gpu_cases():
     cs = []
     for cfg in range(4):
-        cs += cfg_cases(cfg)
+        cs += cfg_cases(cfg) + im2col_a_cases(cfg)
+    cs += im2col_b_cases()
     cs += l2_cases()
     for hw in (1, 9, 49):
         cs += gate_pro_cases(hw) + bpro_cases(hw)

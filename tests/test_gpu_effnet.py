@@ -180,6 +180,138 @@ def test_uint8_crops_are_ingested_directly():
         _assert_all_grads(model, osd, training, f"uint8 (training={training})")
 
 
+N_WIDE = 2
+
+
+@pytest.fixture(scope="module")
+def wide_crop_oracle():
+    """N_WIDE crops of integer values (the same numbers as fp32 and as uint8) of the given size through the fp64 oracle, once per
+    (size, mode), shared by both source kinds.  At 513 only the features: the engine's backward refuses that size."""
+    cache = {}
+
+    def get(size, training):
+        if (size, training) not in cache:
+            x8 = torch.randint(0, 256, (N_WIDE, size, size, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(size))
+            side = -(-size // 32)
+            gw = torch.randn(N_WIDE, 1280, side, side, generator=torch.Generator().manual_seed(13)) * 0.1
+            sd = synth.effnet_b0_state(2)
+            osd = {k: (v.double().requires_grad_("running_" not in k) if v.is_floating_point() else v) for k, v in sd.items()}
+            if size % 32:
+                with torch.no_grad():
+                    fo = O.effnet_b0_forward(osd, x8.double().permute(0, 3, 1, 2), training=training)
+            else:
+                fo = O.effnet_b0_forward(osd, x8.double().permute(0, 3, 1, 2), training=training)
+                (fo * gw.double()).sum().backward()
+            cache[(size, training)] = (x8, gw, sd, osd, fo.detach())
+        return cache[(size, training)]
+    return get
+
+
+@pytest.mark.parametrize("u8", [False, True], ids=["fp32", "uint8"])
+@pytest.mark.parametrize("training", [False, True], ids=["eval", "train"])
+@pytest.mark.parametrize("size", [513, 544])
+def test_crops_wider_than_the_direct_stem_kernel(size, training, u8, wide_crop_oracle, monkeypatch):
+    """W > 512: the stem's forward is the im2col GEMM (per-element gather over 3-channel fp32 / uint8 crops) with the TF-SAME leading
+    pad of the size -- 1 at 513, where the reference pads (1, 1), 0 at 544, where it pads (0, 1) and the window hangs over the edge --
+    and the backward mt_stem_conv_wgrad's plain kernel with the same pad.  Two crops, so the gather and the train-mode statistics cross
+    an image boundary.  Features in both modes and every parameter gradient against the oracle, by the gates of
+    test_uint8_crops_are_ingested_directly.
+
+    Scope: the engine serves square crops of the model's image_size only (each MBConv spec holds one size for both axes), so the
+    non-square crops 96 x 160, 97 x 161 and 64 x 544 are not run; test_crops_of_another_shape_are_refused_before_anything_runs pins
+    that they are refused.  The fallback is reached with square models of image_size 513 (odd: leading pad 1) and 544 (even, wide).
+    513 halves to odd sizes, which the backward's stride-2 depthwise layers do not take: there only the features are checked, and the
+    backward must refuse before it allocates its gradient buffer, records or launches anything."""
+    from mintime_amd import effnet_backward as EB, lib as L
+    x8, gw, sd, osd, fo = wide_crop_oracle(size, training)
+    m = EfficientNet.from_name("efficientnet-b0", drop_connect_rate=0.0, image_size=size)
+    m.load_state_dict(sd, strict=True)
+    m.train(training)
+    m = m.cuda()
+    x = x8.permute(0, 3, 1, 2)
+    f = m((x if u8 else x.float()).cuda())
+    assert f.shape == fo.shape
+    assert_close(f, fo, REL_TOL, f"{size} x {size} features vs oracle (training={training})")
+    if size % 32:
+        calls = []
+        zero_grads = L.zero_grads
+        monkeypatch.setattr(L, "zero_grads", lambda *a, **k: (calls.append("zero_grads"), zero_grads(*a, **k))[1])
+        monkeypatch.setattr(L.mt, "dwconv_bwd", lambda *a, **k: calls.append("dwconv_bwd"))
+        monkeypatch.setattr(L.mt, "bn_act_bwd", lambda *a, **k: calls.append("bn_act_bwd"))
+        last_run = dict(EB.LAST_RUN)
+        with pytest.raises(NotImplementedError, match="odd sizes"):
+            (f * gw.cuda()).sum().backward()
+        torch.cuda.synchronize()
+        assert calls == []
+        assert EB.LAST_RUN == last_run
+        assert L.recording() is None
+        assert all(p.grad is None for p in m.parameters())
+        return
+    (f * gw.cuda()).sum().backward()
+    _assert_all_grads(m, osd, training, f"{size} x {size} (training={training})")
+
+
+def test_backward_refusal_of_odd_sizes_follows_what_is_frozen():
+    """The odd-size refusal concerns only the stride-2 blocks whose mt_dwconv_bwd the walk would launch.  At 513, with the last stride-2
+    block and everything under it frozen, the backward runs and stops above that block; with only that block's project conv
+    trainable as well, the walk enters the block but needs neither its depthwise weight gradient nor a data gradient under it, and
+    still runs; once its depthwise weight is trainable the backward refuses, naming the block, and leaves no gradient behind."""
+    from mintime_amd import effnet_backward as EB
+    m = EfficientNet.from_name("efficientnet-b0", drop_connect_rate=0.0, image_size=513)
+    m.load_state_dict(synth.effnet_b0_state(2), strict=True)
+    m.train(True)
+    m = m.cuda()
+    top = [bi for bi, b in enumerate(m._blocks) if b.spec.s == 2][-1]
+    named = dict(m.named_parameters())
+    for n_, p in named.items():
+        p.requires_grad_(n_.startswith(("_conv_head", "_bn1"))
+                         or any(n_.startswith(f"_blocks.{bi}.") for bi in range(top + 1, len(m._blocks))))
+    x = torch.randint(0, 256, (1, 3, 513, 513), dtype=torch.uint8, generator=torch.Generator().manual_seed(4)).cuda()
+
+    def step():
+        m.zero_grad(set_to_none=True)
+        m(x).sum().backward()
+        torch.cuda.synchronize()
+
+    step()
+    assert EB.LAST_RUN["blocks_run"] == len(m._blocks) - top - 1
+    proj = named[f"_blocks.{top}._project_conv.weight"]
+    proj.requires_grad_(True)
+    step()
+    assert EB.LAST_RUN["blocks_run"] == len(m._blocks) - top
+    assert proj.grad is not None and bool(torch.isfinite(proj.grad).all()) and float(proj.grad.abs().max()) > 0
+    named[f"_blocks.{top}._depthwise_conv.weight"].requires_grad_(True)
+    last_run = dict(EB.LAST_RUN)
+    with pytest.raises(NotImplementedError, match=rf"blocks \[{m._blocks[top].spec.idx}\] see odd sizes"):
+        step()
+    assert EB.LAST_RUN == last_run
+    assert all(p.grad is None for p in m.parameters())
+
+
+@pytest.mark.parametrize("H,W", [(96, 160), (97, 161), (64, 544), (96, 161)])
+def test_crops_of_another_shape_are_refused_before_anything_runs(H, W, monkeypatch):
+    """The engine's row counts come from the model's square image_size: a crop of any other shape -- equal parity (96 x 160, 97 x 161),
+    wider than the direct stem kernel (64 x 544) or of mixed parity (96 x 161, which no stem kernel and no conv_pad expresses) -- would
+    walk the blocks over rows the stem never wrote.  effnet_forward itself says so, naming H and W, before it allocates or launches
+    anything, and so does the module's forward; no parameter's .grad is touched."""
+    from mintime_amd import effnet_engine, lib as L
+    m, _ = _model(2, True)
+    for p in m.parameters():
+        p.grad = torch.full_like(p, 3.0)
+    calls = []
+    monkeypatch.setattr(L, "gemm", lambda *a, **k: calls.append("gemm"))
+    monkeypatch.setattr(L.mt, "stem_conv_fwd", lambda *a, **k: calls.append("stem_conv_fwd"))
+    monkeypatch.setattr(effnet_engine, "_new", lambda *a, **k: calls.append("_new"))
+    for x in (torch.zeros(2, H, W, 3, device="cuda"), torch.zeros(2, H, W, 3, dtype=torch.uint8, device="cuda")):
+        with pytest.raises(ValueError, match=rf"H = {H} by W = {W}"):
+            effnet_engine.effnet_forward(m, x, effnet_engine.param_list(m), True, True)
+        with pytest.raises(ValueError, match=rf"{H}, {W}"):
+            m(x.permute(0, 3, 1, 2))
+    torch.cuda.synchronize()
+    assert calls == []
+    assert all(bool((p.grad == 3.0).all()) for p in m.parameters())
+
+
 def _assert_all_grads(model, osd, training, what):
     """Every EfficientNet parameter gradient vs the oracle's.  In train mode d/d(_bn2.bias) is analytically zero (a per-channel
     shift of a block output is removed by the train-mode BatchNorm behind the next 1x1 conv): both sides hold rounding noise."""

@@ -18,6 +18,14 @@ How each variant is reached, and how that was confirmed from the code:
     M >= 4096 (BN_SWISH_GATE), and neither takes a B prologue.  MT_FORCE_CFG = 0..3 (read per call by pick_cfg) forces the
     128 x 128, 128 x 64, 256 x 32 and 64 x 64 tile; without it N 72 / 68 pad to 128 columns with either width -> 128 x 128;
     N 40 / 136 -> 128 x 64; GEGLU_BWD -> 64 x 64.
+  * im2col forms: try_launch_split and try_launch_dma return 1 for MT_PRO_IM2COL and for any B prologue, so every case lands in
+    gemm_kernel.  gemm.hip takes the granule form (per-unit window origin + 32-bit tap mask on the A side; per-unit pixel cursor on the
+    B side) for an fp32 image with C % 4 == 0 and k k <= 32, else the per-element gather im2col_gather4 (3 channels, uint8, 7 x 7).
+    A side: MT_FORCE_CFG = 0..3 as above.  B side (TN, BN_BWD, ATOMIC): Cout <= 64 with 192 < columns <= 288 takes the one-tile
+    64 x 288 configuration -- CFG_WG64K (two K groups of six wavefronts), CFG_WG64 in deterministic mode -- with either gather;
+    Cout 68 at 288 columns and 192 columns take pick_cfg's 128 x 64, 72 columns 128 x 128, 28 columns 256 x 32.  split_k 3 gives
+    K ranges of a multiple of 16 pixels (split_k_ranges), which start inside an image row unless Wo is 16 (test_gemm_ref_host.py
+    pins that); split_k 0 is one range below 512 pixels.
   * L2-blocked order: tile_grid (gemm_geometry.hpp) gives group_n > 0 from 32 row tiles and 2 column tiles on; at 64 x 64,
     M 2116 = 34 row tiles (XCD bands of 5, 5, 4, ... rows: padding blocks), N 132 = 3 column tiles, group_n = 2 MB / (64 K 4 B): 2 at
     K 4092 (the last group one tile wide), 1 at K 4100 (test_gemm_ref_host.py pins both through mt_debug_tile_grid).
@@ -120,6 +128,9 @@ def _launch(case, fig, split=None):
             fig.true(f"{name}: nothing outside the output slice was touched", torch.equal(_bits(after)[~written], _bits(before)[~written]))
             got[name] = after[:, G.OFF:G.OFF + b.cols[name]][idx]
             fig.true(f"{name}: no NaN left", not bool(torch.isnan(got[name]).any()))
+    if c.bpro == R.BPRO_IM2COL:         # the virtual matrix is exactly zero from k k C on: nothing but +0.0 is ever added there
+        pad_cols = got["C"][:, c.taps:]
+        fig.true("C: the padding columns keep the canary exactly", torch.equal(_bits(pad_cols), _bits(torch.full_like(pad_cols, G.CANARY))))
     return got
 
 
@@ -255,6 +266,29 @@ def test_geglu_bwd_nt_and_nn(n_half, monkeypatch):
     _run(G.geglu_bwd_cases(n_half), monkeypatch)
 
 
+# ---- (a') the im2col forms of the register-staged kernels ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("cfg", [0, 1, 2, 3])
+def test_im2col_forward(cfg, monkeypatch):
+    """MT_PRO_IM2COL with STORE and STATS on each of the four tiles: the granule form (window origin + tap mask per unit) and the
+    per-element gather (3 channels, uint8, k k > 32), over images with H != W, windows that hang over the bottom / right edge,
+    padding >= k, a strided 1 x 1 and K up to 576; the image is a dense tensor inside a noise-filled allocation, the packed weights
+    hold noise in their padding columns (tests/gemm_cases.py IM2COL_A)."""
+    _run(G.im2col_a_cases(cfg), monkeypatch)
+
+
+IM2COL_B_GROUPS = sorted({g[0] for g in G.IM2COL_B})
+
+
+@pytest.mark.parametrize("group", IM2COL_B_GROUPS)
+def test_im2col_weight_gradient(group, monkeypatch):
+    """MT_BPRO_IM2COL (TN, BN_BWD on A, ATOMIC onto a canary) at split_k 1, 3 and auto: the granule form's pixel cursor across image
+    rows shorter than, equal to and longer than the k-step, across images and from a K range that starts inside a row; the one-tile
+    64 x 288 configuration (CFG_WG64K here, CFG_WG64 in deterministic mode) and the shapes just outside it; the per-element gather
+    over fp32 and uint8 crops (tests/gemm_cases.py IM2COL_B)."""
+    _run([c for c in G.im2col_b_cases() if c.name.startswith(f"im2col wgrad {group} ")], monkeypatch)
+
+
 # ---- (b) LDS-DMA kernels -----------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("variant", [0, 1, 2, 3, 4])
@@ -300,6 +334,8 @@ def _det_groups():
     groups = {"register-staged": a, "dma": [c for v in range(5) for c in G.dma_cases(v)], "split-highest": G.split_cases("highest"),
               "split-high": G.split_cases("high")}
     groups["other forms"] = G.extra_cases()
+    for g in IM2COL_B_GROUPS:
+        groups[f"im2col wgrad {g}"] = [c for c in G.im2col_b_cases() if c.name.startswith(f"im2col wgrad {g} ")]
     groups = {k: [c for c in v if c.epi == R.EPI_ATOMIC] for k, v in groups.items()}
     groups["geglu_bwd"] = [c for nh in (64, 192) for c in G.geglu_bwd_cases(nh)]
     return groups
@@ -355,3 +391,28 @@ def test_refusals_launch_nothing():
     _refused(MT_ERR_UNSUPPORTED, L.OP_NT, 16, 16, 8, 8, 8, epilogue=L.EPI_SE_RED, epi=e5, C2=z, ldc2=16, **bn)   # SE_RED on NT
     _refused(MT_ERR_ARG, L.OP_NT, 16, 16, 8, 8, 8, b_prologue=L.BPRO_BN_SWISH_GATE, b_scale=vec, b_shift=vec, b_gate=z, b_hw=4)
     _refused(MT_ERR_ARG, L.OP_NT, 16, 64, 8, 8, 8, epilogue=L.EPI_GEGLU, n_half=32, C2=z, ldc2=64)  # GEGLU: n_half % 64
+    # the im2col forms: one 8 x 8 x 4 image, 3 x 3 at pad 1 -> 64 pixels by 36 columns; the forward as NT 64 x 16 x 36, the weight
+    # gradient as TN 16 x 36 x 64
+    geo = (8, 8, 4, 8, 8, 3, 1, 1, 0)
+    fwd = lambda code, K=36, **kw: _refused(code, L.OP_NT, 64, 16, K, K, K, **{"prologue": L.PRO_IM2COL, "conv": geo, **kw})
+    wg = lambda code, op=L.OP_TN, N=36, **kw: _refused(code, op, 16, N, 64, 16, N, **{"b_prologue": L.BPRO_IM2COL, "conv": geo,
+                                                                                    "epilogue": L.EPI_ATOMIC, **bn, **kw})
+    fwd(MT_ERR_UNSUPPORTED, conv=geo + (1,))                                                        # a uint8 source with C % 4 == 0
+    wg(MT_ERR_UNSUPPORTED, conv=geo + (1,))
+    wg(MT_ERR_ARG, op=L.OP_NT)                                                                      # B prologue on anything but TN
+    wg(MT_ERR_ARG, op=L.OP_NN)
+    wg(MT_ERR_UNSUPPORTED, prologue=L.PRO_NONE)                                                     # ... without BN_BWD on A
+    wg(MT_ERR_UNSUPPORTED, epilogue=L.EPI_STORE)                                                    # ... into anything but ATOMIC
+    for e in (L.EPI_ATOMIC, L.EPI_ACCUM, L.EPI_BIAS_RES):                                           # A prologue: STORE / STATS only
+        fwd(MT_ERR_UNSUPPORTED, epilogue=e, R=z, ldr=64)
+    fwd(MT_ERR_ARG, conv=None)                                                                      # no geometry
+    fwd(MT_ERR_ARG, conv=(8, 8, 4, 8, 8, 0, 1, 1, 0))
+    wg(MT_ERR_ARG, conv=(8, 8, 4, 8, 0, 3, 1, 1, 0))
+    fwd(MT_ERR_ARG, scale=vec)                                                                      # a scale without a shift
+    fwd(MT_ERR_ARG, shift=vec)
+    wg(MT_ERR_ARG, b_scale=vec)
+    fwd(MT_ERR_ARG, conv=(0, 8, 4, 8, 8, 3, 1, 1, 0))                                               # an image without rows / columns
+    fwd(MT_ERR_ARG, conv=(8, -8, 4, 8, 8, 3, 1, 1, 0))
+    wg(MT_ERR_ARG, conv=(8, 0, 4, 8, 8, 3, 1, 1, 0))
+    fwd(MT_ERR_ARG, K=32)                                                                           # fewer columns than k k C = 36
+    wg(MT_ERR_ARG, N=32)

@@ -96,6 +96,72 @@ def test_all_parameter_gradients_vs_oracle(training):
     print("worst relative gradient error vs fp64", worst)
 
 
+WIDE = 514          # the narrowest crop that leaves the direct conv1 kernels (W <= 512) for the im2col GEMMs
+
+
+@pytest.fixture(scope="module")
+def wide_crop_oracle():
+    """One 514 x 514 crop of integer values (the same numbers as fp32 and as uint8) through the oracle, computed once per mode and
+    shared by both source kinds: eval features in fp64; train features and every parameter gradient in fp64 and, as the yardstick of
+    test_all_parameter_gradients_vs_oracle, in fp32."""
+    x8 = torch.randint(0, 256, (1, WIDE, WIDE, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(11))
+    x = x8.permute(0, 3, 1, 2)
+    sd = synth.xception_state(4)
+    cache = {}
+
+    def get(training):
+        if training not in cache:
+            def run(dt, grads):
+                o = {k: (v.to(dt).requires_grad_(grads and "running_" not in k and not k.startswith("fc")) if v.is_floating_point() else v)
+                     for k, v in sd.items()}
+                f = O.xception_forward(o, x.to(dt), training=training)
+                if grads:
+                    (f * wgt.to(dt)).sum().backward()
+                return o, f.detach()
+            side = (((WIDE - 3) // 2 + 1 - 2) + 15) // 16
+            wgt = torch.randn(1, 2048, side, side, generator=torch.Generator().manual_seed(12)) * 0.1
+            o64, f64 = run(torch.float64, training)
+            o32 = run(torch.float32, True)[0] if training else None
+            cache[training] = (wgt, f64, o64, o32)
+        return cache[training]
+    return x8, sd, get
+
+
+@pytest.mark.parametrize("u8", [False, True], ids=["fp32", "uint8"])
+@pytest.mark.parametrize("training", [False, True], ids=["eval", "train"])
+def test_wide_crop_takes_the_im2col_path(training, u8, wide_crop_oracle):
+    """W > 512: conv1's forward is the per-element im2col gather (3 channels; uint8 read as it is) and, in train mode, its weight
+    gradient the TN GEMM with a gathered uint8 / fp32 B operand.  Features in both modes and every parameter gradient in train mode
+    against the oracle, by the gates of test_all_parameter_gradients_vs_oracle."""
+    x8, sd, get = wide_crop_oracle
+    wgt, ofeat, osd, o32 = get(training)
+    model = xception(num_classes=1, pretrain_path=None)
+    model.load_state_dict(sd, strict=True)
+    model.train(training)
+    model = model.cuda()
+    x = x8.permute(0, 3, 1, 2)
+    x = (x if u8 else x.float()).cuda()
+    if not training:
+        with torch.no_grad():
+            feat = model(x)
+        assert feat.shape == ofeat.shape
+        assert_close(feat, ofeat, REL_TOL, "features (eval)")
+        return
+    feat = model(x)
+    (feat * wgt.cuda()).sum().backward()
+    assert_close(feat, ofeat, REL_TOL, "features (train)")
+    for k, p in model.named_parameters():
+        if k.startswith("fc"):
+            assert p.grad is None
+            continue
+        ref = osd[k].grad
+        if k.endswith(".bias") and float(ref.norm()) < 1e-9 * float(osd[k.replace(".bias", ".weight")].grad.norm() + 1e-30):
+            continue
+        rl2 = lambda a: float((a.detach().cpu().double() - ref).norm() / ref.norm())
+        floor, ours = rl2(o32[k].grad), rl2(p.grad)
+        assert ours <= 3 * REL_TOL + 3 * floor, f"grad {k}: ours {ours:.2e} vs fp32-reference floor {floor:.2e}"
+
+
 def test_uint8_crops_are_ingested_directly():
     """Next-row f2: conv1's im2col gather reads uint8 crops; features and conv1's weight gradient equal the fp32-input run."""
     outs = []
