@@ -664,8 +664,10 @@ int mt_baseline_head_bwd(const float* dlogits, const float* pooled, const float*
  *          part holds mt_conv3d_part_floats(d) floats.
  *   dgrad: dx[r][ci] (+)= sum dy[out(r, tap)][co] * wt[tap][co][ci]  (wt = weight permuted to [kt][kh][kw][K][C]); a gather, so
  *          every stride works without atomics.  dx is the gradient of pro(x) (the caller applies the BatchNorm-ReLU adjoint).
- *   wgrad: dw[co][tap][ci] = sum_m dy[m][co] * pro(x)[in(m, tap)][ci]  (written); split over rows into ws (splits * K * taps * C
- *          floats; splits = mt_conv3d_wgrad_splits(d)) and added in split order.
+ *   wgrad: dw[co][tap][ci] = sum_m dy[m][co] * pro(x)[in(m, tap)][ci]  (written); split over rows into ws and added in split order.
+ *          splits: any count from 1 (mt_conv3d_wgrad_splits(d) is the planner's choice, not a requirement), with ws of
+ *          splits * K * taps * C floats for splits > 1 (else ws may be NULL).  The rows are dealt in equal parts rounded up to whole
+ *          steps of 16, so only the first nsplit <= splits slabs of ws are used; one part (nsplit == 1) writes dw directly.
  * mt_sf_bn_relu_fwd: y = relu(z * scale + shift + r), r = res * rscale + rshift (rscale given), res, or 0 (res NULL).
  * mt_sf_bn_relu_bwd_stats / _apply: the BatchNorm(+ReLU) adjoint.  du = g * mask with mask = (z * scale + shift > 0) when scale is
  *   given, (m > 0) when m is given, else 1.  stats [2][C] (fp64, written) = (sum du, sum du * (z - mean) * invstd) for
