@@ -842,6 +842,75 @@ int mt_crop_resize_u8(const unsigned char* src, int64_t src_bytes, int N, int H,
                       int* err, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * MTCNN face detector, inference only (csrc/mtcnn.hip): what the reference's FacenetDetector runs in front of everything else,
+ * facenet_pytorch's MTCNN(thresholds, margin = 0).detect(frames, landmarks = False) (preprocessing/face_detector.py:38-56), from the
+ * uint8 frames [N][H][W][3] to boxes without a host read.  UNCHECKED against the package or a checkpoint: facenet_pytorch is not
+ * available where this was written; networks, key names and post-processing are restated by hand from its published source.
+ *
+ * Records.  Every list holds records of 12 floats: x1 y1 x2 y2 score reg[4] key 0 0 (key: int32 bits).  Lists are segments
+ * [segs][cap] of records with a device int32 count per segment; a count above cap means the list overflowed and every reader
+ * clamps it.  key = level << 24 | (y Wm + x) names the P-Net map position the box came from.
+ * Defined deviations from the package: (a) equal scores in an NMS order are broken by key ascending (the package: an unstable sort);
+ * (b) NMS runs per image on the coordinates themselves (torchvision offsets every box by image * (max + 1) first); (c) a stage-2/3
+ * window without a pixel (ey <= y - 1 or ex <= x - 1) gets no score and is dropped (the package fails on it); (d) lists have
+ * capacities, and an overflow sets a bit of the sticky device word `err` and drops what does not fit, nothing is written outside.
+ *
+ * area_resize(in -> out), per axis: output cell i averages source indices floor(i in / out) .. ceil((i + 1) in / out) - 1
+ *   (F.interpolate(mode = "area")); a pixel is (sum / count - 127.5) * 0.0078125 with an exact integer sum and one fp32 division.
+ *
+ * mt_mtcnn_pnet: ONE pyramid level of N frames, fused: the level (Hs x Ws = int(H s + 1) x int(W s + 1), at least 12 x 12) is
+ *   resampled tile by tile into LDS and P-Net runs on it there -- conv1 3->10 k3, PReLU, MaxPool(2, 2, ceil_mode), conv2 10->16 k3,
+ *   PReLU, conv3 16->32 k3, PReLU, conv4_1 (2, softmax, prob = channel 1) and conv4_2 (4 = reg); map Hm = ceil((Hs - 2) / 2) - 4.
+ *   One block = 16 x 16 map positions, 256 threads, 59 KB of LDS.  Every output is bias + a chain of fused multiply-adds in
+ *   ascending (ky, kx, ci) order: a function of the layer alone, never of N, the tile or the level size; to first order
+ *   |y - exact| <= (n + 1) 2^-24 sum |x w| per layer of reduction length n, on top of the error its inputs carry.
+ *   weights: 6632 floats -- w1 [3][3][3][10], b1, a1 (PReLU), w2 [3][3][10][16], b2, a2, w3 [3][3][16][32], b3, a3,
+ *   w4 [32][6] (conv4_1 then conv4_2), b4 -- i.e. every filter as [ky][kx][ci][co].
+ *   A position with prob >= thr is appended to segment n * levels + level of rec (cap records each) through one LDS counter per
+ *   block and one integer atomic per block on counts[]; box = floor((2x + 1) / scale), floor((2y + 1) / scale),
+ *   floor((2x + 12) / scale), floor((2y + 12) / scale), fp32 with a correctly rounded division.  The append order is not defined;
+ *   overflow sets bit 0 of *err.  dbg_level [N][Hs][Ws][3] and dbg_maps [N][5][Hm][Wm] (prob, reg0..3), NULL outside the tests,
+ *   additionally receive the level and the maps.  counts are NOT cleared here.
+ * mt_mtcnn_nms: greedy NMS of `segs` ragged segments, one wavefront each, cap_in <= 1024.  Rows with score < 0 are dropped first.
+ *   Order: score descending, key ascending.  form 0 (torchvision): area = (x2 - x1)(y2 - y1), inter = max(0, xx2 - xx1) max(0, yy2 -
+ *   yy1), a box goes when inter / (a_kept + a - inter) > thr.  form 1 (the package's numpy form, method Min): + 1 on every
+ *   difference, inter / min(a_kept, a) > thr.  Products and the division are rounded on their own (no fused multiply-add, no
+ *   reciprocal), so decisions are those of fp32 CPU arithmetic.  The kept records of segment g are written, in kept order, to
+ *   segment g / group of rec_out: group == 1 at its start with count_out[g] = kept; group > 1 appended at
+ *   atomicAdd(count_out[g / group], kept), so the caller clears count_out and the order among the group's members is not defined.
+ *   What does not fit cap_out is dropped and sets err_bit (a mask) in *err.  picks [segs][cap_in] or NULL: the input rows kept, in
+ *   order, then -1.
+ * mt_mtcnn_boxes: one thread per record, every operation rounded on its own, in this order.  mode 1 (stage 1): w = x2 - x1,
+ *   h = y2 - y1; x1 += r0 w, y1 += r1 h, x2 += r2 w, y2 += r3 h; rerec.  mode 2 (stage 2): the same with w, h + 1 (bbreg); rerec.
+ *   mode 3 (stage 3): bbreg, no rerec.  mode 0: nothing.  rerec: l = max(w, h) of the new box; x1 += 0.5 w - 0.5 l, y1 += 0.5 h -
+ *   0.5 l, x2 = x1 + l, y2 = y1 + l.  Then, if win [segs][cap][4] int32 is given, pad: truncate toward zero; x = max(x1, 1),
+ *   y = max(y1, 1), ex = min(x2, W), ey = min(y2, H), stored as (x, y, ex, ey); rows past the count get zeros.
+ * mt_mtcnn_crop: window rows y-1 .. ey-1, columns x-1 .. ex-1 of frame `seg` -> out [N * cap][S][S][4] fp32, area_resize'd and
+ *   normalised, 4th channel 0 (the input rows of mt_conv2d_fwd).  Rows past the count and windows without a pixel come out zero.
+ * mt_mtcnn_prelu_pool: y = MaxPool(k, s, ceil_mode)(PReLU(x)) of channels-last rows x [rows][H][W][C], one slope per channel,
+ *   C % 4 == 0, k in 1..3 (k = 1: PReLU alone).  counts != NULL: row r is skipped unless r % cap < counts[r / cap].
+ * mt_mtcnn_score: head [segs * cap][ldh] = logits 0, 1 and reg 0..3 (the two dense heads stacked along K) -> rec: score =
+ *   softmax(logits)[1] if it is > thr (strict) and the row's window holds a pixel, else -1; reg.
+ * mt_mtcnn_finalize: the per-image lists rec [N][cap] -> boxes [max_faces][4], probs, frame_index (-1 on unused rows), *count,
+ *   image_counts [N], image-major; rows that do not fit set err_bit in *err.  N <= 4096.
+ * No entry point issues a floating-point atomic.  Nothing is launched or written on an argument error.
+ * ------------------------------------------------------------------------------------------------ */
+int mt_mtcnn_pnet(const unsigned char* frames, int N, int H, int W, int Hs, int Ws, float scale, int level, int levels,
+                  const float* weights, float thr, float* rec, int* counts, int cap, int* err, float* dbg_level, float* dbg_maps,
+                  void* stream);
+int mt_mtcnn_nms(const float* rec_in, const int* count_in, int segs, int cap_in, int group, int form, float thr, float* rec_out,
+                 int* count_out, int cap_out, int* picks, int* err, int err_bit, void* stream);
+int mt_mtcnn_boxes(float* rec, const int* counts, int segs, int cap, int mode, int H, int W, int* win, void* stream);
+int mt_mtcnn_crop(const unsigned char* frames, int N, int H, int W, const int* win, const int* counts, int cap, int S, float* out,
+                  void* stream);
+int mt_mtcnn_prelu_pool(const float* x, float* y, const float* slope, int64_t rows, int H, int W, int C, int k, int s, const int* counts,
+                        int cap, void* stream);
+int mt_mtcnn_score(const float* head, int ldh, float* rec, const int* win, const int* counts, int segs, int cap, int H, int W, float thr,
+                   void* stream);
+int mt_mtcnn_finalize(const float* rec, const int* counts, int N, int cap, int max_faces, float* boxes, float* probs, int* frame_index,
+                      int* count, int* image_counts, int* err, int err_bit, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Launch plans (the caller side of the step: reference train.py:332-378, the Python loop that issues every op).
  * A plan holds the SEQUENCE of entry-point calls of one phase (EfficientNet forward, TimeSformer forward, TimeSformer backward,
  * EfficientNet backward) so that the host issues a phase with one call instead of hundreds through its FFI.

@@ -31,7 +31,9 @@ from . import facenet, facenet_engine  # noqa: F401,E402
 from .facenet import InceptionResnetV1, fixed_image_standardization  # noqa: F401,E402
 from . import face_crops  # noqa: F401,E402
 from .face_crops import FaceCropPlan, FaceCrops, resize_crops  # noqa: F401,E402
+from . import mtcnn, mtcnn_engine  # noqa: F401,E402
+from .mtcnn import MTCNN, Detections  # noqa: F401,E402
 
-__all__ = ["face_crops", "FaceCropPlan", "FaceCrops", "resize_crops", "facenet", "InceptionResnetV1", "fixed_image_standardization","arch", "synth", "lib", "timesformer", "tsf_engine", "SizeInvariantTimeSformer", "efficientnet", "effnet_engine", "EfficientNet",
+__all__ = ["mtcnn", "MTCNN", "Detections", "face_crops", "FaceCropPlan", "FaceCrops", "resize_crops", "facenet", "InceptionResnetV1", "fixed_image_standardization","arch", "synth", "lib", "timesformer", "tsf_engine", "SizeInvariantTimeSformer", "efficientnet", "effnet_engine", "EfficientNet",
            "baseline", "Baseline", "slowfast", "SlowFast", "slowfast_r50", "slowfast_input_transform", "metrics", "EpochMetrics", "identities", "ClusterPlan", "IdentityClusters",
            "cluster_embeddings", "cluster_similarities", "identities_from_labels", "set_matmul_precision", "get_matmul_precision", "matmul_precision"]

@@ -15,7 +15,7 @@ UNCHECKED against facenet_pytorch: the package is not available where this was w
 are restated by hand from its published source and have not been compared with the package or a real checkpoint.
 
 Not covered: `classify=True` (the `logits` layer is held for the state dict and never launched), training / fine-tuning (no backward),
-downloading weights, MTCNN, the PIL resize of ragged crops.  The returned [T, 512] tensor is a buffer of the module, overwritten by
+downloading weights.  (The detector is mtcnn.py, the crops face_crops.py.)  The returned [T, 512] tensor is a buffer of the module, overwritten by
 the next call with the same T; H and W of at least 75.  There is no CPU path."""
 import torch
 from torch import nn

@@ -171,6 +171,14 @@ LAUNCHES = {
     "mt_l2_normalize_rows": [f32p, i64, f32p, i64, i64, C.c_int, C.c_float, C.c_void_p],
     "mt_face_rects": [f32p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4,
     "mt_crop_resize_u8": [C.c_void_p, i64] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 3,
+    "mt_mtcnn_pnet": [C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int, f32p, C.c_float, f32p, C.c_void_p, C.c_int, C.c_void_p,
+                      f32p, f32p, C.c_void_p],
+    "mt_mtcnn_nms": [f32p, C.c_void_p] + [C.c_int] * 4 + [C.c_float, f32p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "mt_mtcnn_boxes": [f32p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p],
+    "mt_mtcnn_crop": [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, f32p, C.c_void_p],
+    "mt_mtcnn_prelu_pool": [f32p, f32p, f32p, i64] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p],
+    "mt_mtcnn_score": [f32p, C.c_int, f32p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p],
+    "mt_mtcnn_finalize": [f32p, C.c_void_p] + [C.c_int] * 3 + [f32p, f32p] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p],
     "mt_memset_async": [C.c_void_p, C.c_int, i64, C.c_void_p],
     "mt_copy_async": [C.c_void_p, C.c_void_p, i64, C.c_void_p],
 }
