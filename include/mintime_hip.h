@@ -464,20 +464,26 @@ int mt_conv1x1_bwd_fused_supported(int Cout, int Cin);
  *   mode 1: du_d = (da*gate + dpooled/hw) * swish'(z_d*scale + shift), plus its BatchNorm-backward sums (stats like MT_EPI_STATS,
  *           second sum = du_d * (z_d - mean) * invstd)
  * Replaces mt_conv1x1_rows (mode 2) + the reduction of mt_se_bwd + mt_bn_act_bwd: 3 instead of 6 passes over the expanded tensor.
- * w_p [Co, C] (Co <= 32; C = 32 / 96 / 144), hw % 64 == 0, rows % hw == 0. */
+ * w_p [Co, C] (Co <= 32; C = 32 / 96 / 144), hw % 64 == 0, rows > 0 and rows % hw == 0 (else MT_ERR_ARG).  Read as float4, so 16-byte aligned
+ * (else MT_ERR_ARG): du_p, z_p, kabc_p, z_d, scale_d, shift_d, and in mode 1 gate, dpooled, mean_invstd_d, du_d.  stats [|slots|][2][C]; a
+ * negative slot count selects the integer-limb accumulators (see mt_set_deterministic above). */
 int mt_se_stage_fused_supported(int Co, int C, int hw);
 int mt_se_stage_fused(const float* du_p, const float* z_p, const float* kabc_p, const float* w_p, const float* z_d,
                       const float* scale_d, const float* shift_d, int mode, float* dgate, const float* gate, const float* dpooled,
                       const float* mean_invstd_d, float* du_d, double* stats, int slots, int64_t rows, int Co, int C, int hw,
                       void* stream);
+/* mt_conv1x1_bwd_fused: rows > 0 (else MT_ERR_ARG); du, kabc, x, res, dx 16-byte aligned (else MT_ERR_ARG). */
 int mt_conv1x1_bwd_fused(const float* du, const float* kabc, const float* x, const float* w, const float* res, float* dx,
                          float* dw, int64_t rows, int Cout, int Cin, void* stream);
+/* mt_conv1x1_wgrad: rows > 0 (else MT_ERR_ARG); du, z, kabc, x and (when given) gate 16-byte aligned (else MT_ERR_ARG); hw may be
+ * any positive value, also above rows (gate then holds one image). */
 int mt_conv1x1_wgrad(const float* du, const float* z, const float* kabc, const float* x, const float* sc, const float* sh,
                      const float* gate, int hw, float* dw, int64_t rows, int Cout, int Cin, void* stream);
 /* The same weight gradient for the WIDE project convolutions of the late stages (65-320 output x 224-2048 expanded channels, the gate
  * form only: sc, sh, gate required; hw >= 32): the result is cut into 128-column slabs, one block per (slab, row range), load / transform
  * wavefronts feeding MFMA wavefronts through double-buffered LDS (wide_wgrad.hip).  Replaces mt_gemm (MT_OP_TN with both operand
- * prologues), which re-applied the transforms per fragment read. */
+ * prologues), which re-applied the transforms per fragment read.  rows > 0 and hw >= 32 (else MT_ERR_ARG); du, z, kabc, x, sc, sh, gate
+ * 16-byte aligned (else MT_ERR_ARG). */
 int mt_conv1x1_wgrad_wide_supported(int Cout, int Cin);
 int mt_conv1x1_wgrad_wide(const float* du, const float* z, const float* kabc, const float* x, const float* sc, const float* sh,
                           const float* gate, int hw, float* dw, int64_t rows, int Cout, int Cin, void* stream);
@@ -487,7 +493,10 @@ int mt_conv1x1_wgrad_wide(const float* du, const float* z, const float* kabc, co
  *   amode 0: a = x;   1: a = swish(c0*x + c1) * c2[row / hw]  (c2 = SE gate [rows/hw, Cin]);   2: a = c0*x + c1*x2 + c2 (BatchNorm backward).
  * w is [Cout, ldw] (w_transposed = 0) or the forward weight [Cin, ldw] used transposed (w_transposed = 1, data gradient).
  * stats (optional) receives the BatchNorm sums of `out` like MT_EPI_STATS.  mt_conv1x1_rows_supported tells whether this kernel is
- * the measured better choice for a channel pair and mode (otherwise use mt_gemm). */
+ * the measured better choice for a channel pair and mode (otherwise use mt_gemm); mt_conv1x1_rows itself runs every pair that has an
+ * instance (Cin % 4 == 0 and (ceil(Cin/32), ceil(Cout/32)) one of (1,1) (1,3) (1,5) (3,1)) in every mode.  rows > 0 (else MT_ERR_ARG);
+ * x, x2 and, in amode 1, c2 are read as float4: 16-byte aligned (else MT_ERR_ARG).  stats [|slots|][2][Cout]; a negative slot count
+ * selects the integer-limb accumulators (see mt_set_deterministic above). */
 int mt_conv1x1_rows_supported(int Cin, int Cout, int amode);
 int mt_conv1x1_rows(const float* x, const float* x2, const float* w, int ldw, int w_transposed, const float* c0, const float* c1,
                     const float* c2, int hw, int amode, const float* res, float* out, double* stats, int slots, int64_t rows,

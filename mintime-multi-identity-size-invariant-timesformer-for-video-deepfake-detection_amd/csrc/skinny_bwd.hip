@@ -449,6 +449,7 @@ extern "C" int mt_conv1x1_bwd_fused_supported(int Cout, int Cin) {
 extern "C" int mt_conv1x1_bwd_fused(const float* du, const float* kabc, const float* x, const float* w, const float* res, float* dx,
                                     float* dw, int64_t rows, int Cout, int Cin, void* stream) {
   if (!du || !kabc || !x || !w || !dx || !dw) return fail(MT_ERR_ARG, "mt_conv1x1_bwd_fused: null pointer");
+  if (rows <= 0) return fail(MT_ERR_ARG, "mt_conv1x1_bwd_fused: rows must be positive");
   if (!mt_conv1x1_bwd_fused_supported(Cout, Cin))
     return fail(MT_ERR_UNSUPPORTED, "mt_conv1x1_bwd_fused: no instance for %d -> %d channels", Cout, Cin);
   if (((uintptr_t)du | (uintptr_t)x | (uintptr_t)kabc | (uintptr_t)res | (uintptr_t)dx) & 15) return fail(MT_ERR_ARG, "mt_conv1x1_bwd_fused: 16-byte alignment");

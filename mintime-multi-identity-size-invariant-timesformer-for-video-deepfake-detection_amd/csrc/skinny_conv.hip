@@ -239,11 +239,13 @@ extern "C" int mt_conv1x1_rows(const float* x, const float* x2, const float* w, 
                                const float* c1, const float* c2, int hw, int amode, const float* res, float* out, double* stats,
                                int slots, int64_t rows, int Cin, int Cout, void* stream) {
   if (!x || !w || !out) return fail(MT_ERR_ARG, "mt_conv1x1_rows: null pointer");
+  if (rows <= 0) return fail(MT_ERR_ARG, "mt_conv1x1_rows: rows must be positive");
   if (!rows_shape_built(Cin, Cout)) return fail(MT_ERR_UNSUPPORTED, "mt_conv1x1_rows: no instance for %d -> %d channels", Cin, Cout);
   if (amode == A_GATE && (!c0 || !c1 || !c2 || hw <= 0)) return fail(MT_ERR_ARG, "mt_conv1x1_rows: gate mode needs scale, shift, gate, hw");
   if (amode == A_BNBWD && (!c0 || !c1 || !c2 || !x2)) return fail(MT_ERR_ARG, "mt_conv1x1_rows: BN-backward mode needs ka, kb, kc and z");
   if (amode < 0 || amode > 2) return fail(MT_ERR_ARG, "mt_conv1x1_rows: bad mode");
-  if (((uintptr_t)x | (uintptr_t)x2) & 15) return fail(MT_ERR_ARG, "mt_conv1x1_rows: 16-byte alignment");
+  if ((((uintptr_t)x | (uintptr_t)x2) & 15) || (amode == A_GATE && ((uintptr_t)c2 & 15)))      // what the kernel reads as float4
+    return fail(MT_ERR_ARG, "mt_conv1x1_rows: 16-byte alignment");
   ConvArgs a{x, x2, w, ldw, w_transposed ? 1 : 0, c0, c1, c2, res, out, stats, slots != 0 ? slots : 1, rows, Cin, Cout, hw > 0 ? hw : 1};
   hipStream_t st = (hipStream_t)stream;
   const int kt = (Cin + 31) / 32, nt = (Cout + 31) / 32;

@@ -253,7 +253,10 @@ extern "C" int mt_se_stage_fused(const float* du_p, const float* z_p, const floa
   if (mode == 1 && (!gate || !dpooled || !mean_invstd_d || !du_d || !stats || slots == 0))
     return fail(MT_ERR_ARG, "mt_se_stage_fused: activation mode needs gate, dpooled, mean_invstd, du_d and stats");
   if (mode != 0 && mode != 1) return fail(MT_ERR_ARG, "mt_se_stage_fused: bad mode");
-  if (rows % hw) return fail(MT_ERR_ARG, "mt_se_stage_fused: rows must be a multiple of hw");
+  if (rows <= 0 || rows % hw) return fail(MT_ERR_ARG, "mt_se_stage_fused: rows must be a positive multiple of hw");
+  uintptr_t vec = (uintptr_t)du_p | (uintptr_t)z_p | (uintptr_t)kabc_p | (uintptr_t)z_d | (uintptr_t)scale_d | (uintptr_t)shift_d;      // read as float4
+  if (mode == 1) vec |= (uintptr_t)gate | (uintptr_t)dpooled | (uintptr_t)mean_invstd_d | (uintptr_t)du_d;
+  if (vec & 15) return fail(MT_ERR_ARG, "mt_se_stage_fused: 16-byte alignment");
   SeArgs a{du_p, z_p, kabc_p, w_p, z_d, scale_d, shift_d, dgate, gate, dpooled, mean_invstd_d, du_d, stats, slots, rows, Co, C, hw};
   hipStream_t st = (hipStream_t)stream;
   if (C == 32) return launch_se<1>(a, mode, st);

@@ -320,11 +320,12 @@ extern "C" int mt_conv1x1_wgrad_supported(int Cout, int Cin) {
 extern "C" int mt_conv1x1_wgrad(const float* du, const float* z, const float* kabc, const float* x, const float* sc, const float* sh,
                                 const float* gate, int hw, float* dw, int64_t rows, int Cout, int Cin, void* stream) {
   if (!du || !z || !kabc || !x || !dw) return fail(MT_ERR_ARG, "mt_conv1x1_wgrad: null pointer");
+  if (rows <= 0) return fail(MT_ERR_ARG, "mt_conv1x1_wgrad: rows must be positive");
   if (!mt_conv1x1_wgrad_supported(Cout, Cin))
     return fail(MT_ERR_UNSUPPORTED, "mt_conv1x1_wgrad: %d x %d weights do not fit the accumulator-resident kernel", Cout, Cin);
   const bool g = gate != nullptr;
   if (g && (!sc || !sh || hw <= 0)) return fail(MT_ERR_ARG, "mt_conv1x1_wgrad: gate needs scale, shift and hw");
-  if (((uintptr_t)du | (uintptr_t)z | (uintptr_t)x | (uintptr_t)kabc) & 15) return fail(MT_ERR_ARG, "mt_conv1x1_wgrad: 16-byte alignment");
+  if (((uintptr_t)du | (uintptr_t)z | (uintptr_t)x | (uintptr_t)kabc | (uintptr_t)gate) & 15) return fail(MT_ERR_ARG, "mt_conv1x1_wgrad: 16-byte alignment");
   WgradArgs a{du, z, kabc, x, sc, sh, gate, dw, rows, Cout, Cin, hw, nullptr, 0, 0, 0, 0, 0, 0};
   hipStream_t st = (hipStream_t)stream;
   const int mt_ = (Cout + 31) / 32, nt = (Cin + 31) / 32;
