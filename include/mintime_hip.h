@@ -360,6 +360,14 @@ int mt_layernorm_bwd_rows_sums(const float* dy, const float* x, const float* sta
                                int rows, int dim, void* dx_planes, float* partials, int skip_period, void* stream);
 int mt_layernorm_bwd_cols_reduce(const float* partials, int blocks, int dim, float* dgamma, float* dbeta, float* dx_colsum,
                                  void* stream);
+/* mt_layernorm_bwd_rows_sums with a SPARSE residual gradient: dx_res [rows / period][dim] belongs to the rows r % period == 0
+ * (row r takes dx_res[r / period]); every other row takes none, dx = LN'(dy).  Same dx, dx_planes and partials as the dense form fed
+ * a [rows][dim] tensor that is zero off those rows.  The last layer with its dead rows pruned: the head reads x[:, 0] only (:270-276),
+ * so below that layer's space attention the residual stream's gradient lives on the cls rows (period = 1 + F*n) alone.
+ * rows % period == 0, dim <= 512; anything else returns an error before anything is launched. */
+int mt_layernorm_bwd_rows_sums_sparse(const float* dy, const float* x, const float* stats, const float* gamma, float* dx,
+                                      const float* dx_res, int period, int rows, int dim, void* dx_planes, float* partials,
+                                      int skip_period, void* stream);
 
 /* out[n] += sum_m A[map(m)*lda + n]   (bias gradients). */
 int mt_colsum(const float* A, int64_t lda, mt_rowmap map, int M, int N, float* out, void* stream);
@@ -383,6 +391,14 @@ int mt_embed_bwd(const float* dx, float* dcls, float* dpos_emb, float* dsize_emb
  * fixed-order reduction with one rank per group. */
 int mt_attn_bwd(const float* qkv, const float* dout, float* dqkv, const uint8_t* mask, const uint8_t* ident,
                 int B, int H, int F, int n, int mode, float scale, void* dqkv_planes, void* stream);
+/* The cls query's adjoint (mt_attn_bwd mode 2; autograd of :80-87 / :112-141 for the query x[:, 0] that the head reads, :270-276) with
+ * the COMPLETE plane tensor of dqkv [B*N][3*H*64] as its only output: dk / dv of every key, dq of the cls row, exact zeros in the dq
+ * section of every patch row and in the padding rows (rows rounded up to 32) -- what mt_split_planes_blk makes of mode 2's result in
+ * a zero-filled dqkv, without the fill, the fp32 tensor or the split pass.  Reads row 0 of each clip of dout [B,N,H*64].  One block
+ * per (clip, head), no atomics: the same bits on every run.  n = 1 .. 100 and a 16-byte aligned plane tensor, else an error and
+ * nothing written. */
+int mt_attn_bwd_cls_planes(const float* qkv, const float* dout, const uint8_t* mask, int B, int H, int F, int n, float scale,
+                           void* dqkv_planes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * EfficientNet-B0 backward, everything except the 1x1-convolution dgrad/wgrad (mt_gemm with the BN_BWD prologue).

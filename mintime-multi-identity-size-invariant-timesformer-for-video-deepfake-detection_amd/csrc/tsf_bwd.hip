@@ -230,9 +230,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel4(const float* d
 // four wavefronts meet in 8 KB of LDS once at the end, and the block stores ONE row of partials[blocks][3][D] -- no atomics, no
 // re-read.  layernorm_cols_reduce_kernel (weight-gradient queue) adds the block rows in block order into dgamma / dbeta / dx_colsum:
 // 6 MB read instead of 75, and a fixed summation order (nothing for the deterministic mode to replace).
-__global__ __launch_bounds__(256) void layernorm_bwd_rows_sums_kernel(
+// SPARSE: the incoming residual gradient exists for the rows r % period == 0 only, packed as dx_in[rows / period][D] (the last layer
+// with its dead rows pruned: only the cls rows carry a residual gradient); every other row takes none.  Same arithmetic as the dense
+// form fed zeros there -- without the zero-filled [rows][D] tensor and the pass that reads it.
+template <bool SPARSE>
+__device__ __forceinline__ void layernorm_bwd_rows_sums_body(
     const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
-    float* __restrict__ dx, const float* __restrict__ dx_in, int rows, int D, PlaneRef dxp, float* __restrict__ partials, int skip_period) {
+    float* __restrict__ dx, const float* __restrict__ dx_in, int rows, int D, const PlaneRef& dxp, float* __restrict__ partials,
+    int skip_period, int period) {
   constexpr int NI = 2;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int nwaves = gridDim.x * 4;
@@ -249,14 +254,16 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_sums_kernel(
     const float keep = (skip_period > 0 && row % skip_period == 0) ? 0.f : 1.f;
     const float4* xr = reinterpret_cast<const float4*>(x + (int64_t)row * D);
     const float4* dyr = reinterpret_cast<const float4*>(dy + (int64_t)row * D);
-    const float4* pin = reinterpret_cast<const float4*>(dx_in + (int64_t)row * D);
+    const bool has_res = !SPARSE || row % period == 0;               // (wave-uniform)
+    const float4* pin = reinterpret_cast<const float4*>(dx_in + (int64_t)(SPARSE ? row / period : row) * D);
     float4* dxr = reinterpret_cast<float4*>(dx + (int64_t)row * D);
     float4 xv[NI], d[NI], g[NI], pv[NI];
     float a1 = 0.f, a2 = 0.f;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int q = min(lane + i * 64, nq - 1);
-      xv[i] = xr[q]; d[i] = dyr[q]; g[i] = reinterpret_cast<const float4*>(gamma)[q]; pv[i] = pin[q];
+      xv[i] = xr[q]; d[i] = dyr[q]; g[i] = reinterpret_cast<const float4*>(gamma)[q];
+      pv[i] = has_res ? pin[q] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
@@ -297,6 +304,18 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_sums_kernel(
   meet(dg, 0);
   meet(db, 1);
   meet(ds, 2);
+}
+
+__global__ __launch_bounds__(256) void layernorm_bwd_rows_sums_kernel(
+    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
+    float* __restrict__ dx, const float* __restrict__ dx_in, int rows, int D, PlaneRef dxp, float* __restrict__ partials, int skip_period) {
+  layernorm_bwd_rows_sums_body<false>(dy, x, stats, gamma, dx, dx_in, rows, D, dxp, partials, skip_period, 1);
+}
+__global__ __launch_bounds__(256) void layernorm_bwd_rows_sums_sparse_kernel(
+    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
+    float* __restrict__ dx, const float* __restrict__ dx_res, int period, int rows, int D, PlaneRef dxp, float* __restrict__ partials,
+    int skip_period) {
+  layernorm_bwd_rows_sums_body<true>(dy, x, stats, gamma, dx, dx_res, rows, D, dxp, partials, skip_period, period);
 }
 
 // out_which[c] += sum over blocks of partials[b][which][c], in a FIXED order: 64 columns x 16 phases per block (1024 threads), phase p
@@ -609,9 +628,17 @@ __device__ __forceinline__ float mul_unfused(float a, float b) {
 
 // Lane mapping: 16 lanes per key (lane & 15 = which float4 of the 64-wide head), 16 keys per pass of the block, so every K / V /
 // dK / dV row is one coalesced 256-byte access (one key per lane made each lane walk its own 6 KB-strided row: 105 us per launch).
+// PLANES: the cls query's adjoint is the WHOLE result (mt_attn_bwd_cls_planes: no patch kernel follows), written as the plane tensor of
+// dqkv and nowhere else -- dk / dv of every key and dq of the cls row as above (the same fp32 values, split on the way out), zeros in
+// the dq section of the patch rows; block B*H writes the zero padding rows.  dqkv is not touched, factored is 0.
+template <bool PLANES>
 __global__ __launch_bounds__(CLS_W * 64) void attn_cls_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                                  float* __restrict__ dqkv, const uint8_t* __restrict__ mask,
-                                                                 int B, int H, int F, int n, float scale, int factored) {
+                                                                 int B, int H, int F, int n, float scale, int factored, const PlaneRef dpl) {
+  if (PLANES && (int)blockIdx.x == B * H) {
+    planes_zero_pad(dpl, B * (1 + F * n), threadIdx.x, CLS_W * 64);
+    return;
+  }
   // factored: the patch keys receive only the two scalars of the rank-1 contribution (cls_fact_off); the patch kernel that owns the key
   // multiplies them with the cls query / cls dO rows itself.  Saves writing and re-reading two 64-float rows per key and head (52 + 52
   // MB per call at B = 32).  The cls key's own row (j = 0) stays full: the patch kernels add to it atomically.
@@ -626,7 +653,7 @@ __global__ __launch_bounds__(CLS_W * 64) void attn_cls_bwd_kernel(const float* _
   float* red = ds_ + N;
   float* part = lds + ((2 * N + CLS_W + 3) & ~3);               // 16-byte aligned (float4 slots)
   const float* base = qkv + (int64_t)b * N * ld + h * DH + sub * 4;
-  float* dbase = dqkv + (int64_t)b * N * ld + h * DH + sub * 4;
+  float* dbase = PLANES ? nullptr : dqkv + (int64_t)b * N * ld + h * DH + sub * 4;      // (PLANES: dqkv is NULL and not used)
   float4 q = *reinterpret_cast<const float4*>(base);
   q.x *= scale; q.y *= scale; q.z *= scale; q.w *= scale;
   const float4 dO = *reinterpret_cast<const float4*>(dout + (int64_t)b * N * inner + h * DH + sub * 4);   // row 0
@@ -679,7 +706,12 @@ __global__ __launch_bounds__(CLS_W * 64) void attn_cls_bwd_kernel(const float* _
       if (j < N) {
         const float p = pl_[j];
         const float dS = p * (ds_[j] - delta);
-        if (factored && j > 0) {
+        if constexpr (PLANES) {
+          const int row = b * N + j, col = h * DH + sub * 4;
+          if (j > 0) planes_store4(dpl, row, col, 0.f, 0.f, 0.f, 0.f);
+          planes_store4(dpl, row, inner + col, dS * q.x, dS * q.y, dS * q.z, dS * q.w);
+          planes_store4(dpl, row, 2 * inner + col, p * dO.x, p * dO.y, p * dO.z, p * dO.w);
+        } else if (factored && j > 0) {
           if (sub == 0) {
             float* dclip = dqkv + (int64_t)b * N * ld;
             dclip[cls_fact_off(0, h, H, j, N, inner, ld)] = dS;
@@ -707,7 +739,8 @@ __global__ __launch_bounds__(CLS_W * 64) void attn_cls_bwd_kernel(const float* _
       const float4 u = *reinterpret_cast<const float4*>(part + w * 64 + sub * 4);
       t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
     }
-    *reinterpret_cast<float4*>(dbase) = make_float4(scale * t.x, scale * t.y, scale * t.z, scale * t.w);
+    if constexpr (PLANES) planes_store4(dpl, b * N, h * DH + sub * 4, scale * t.x, scale * t.y, scale * t.z, scale * t.w);
+    else *reinterpret_cast<float4*>(dbase) = make_float4(scale * t.x, scale * t.y, scale * t.z, scale * t.w);
   }
 }
 
@@ -1695,6 +1728,20 @@ extern "C" int mt_layernorm_bwd_rows_sums(const float* dy, const float* x, const
   return check_launch("mt_layernorm_bwd_rows_sums");
 }
 
+extern "C" int mt_layernorm_bwd_rows_sums_sparse(const float* dy, const float* x, const float* stats, const float* gamma, float* dx,
+                                                 const float* dx_res, int period, int rows, int dim, void* dx_planes, float* partials,
+                                                 int skip_period, void* stream) {
+  if (!dy || !x || !stats || !gamma || !dx || !dx_res || !partials) return fail(MT_ERR_ARG, "mt_layernorm_bwd_rows_sums_sparse: null pointer");
+  if (dim <= 0 || (dim & 3) || dim > 512) return fail(MT_ERR_UNSUPPORTED, "mt_layernorm_bwd_rows_sums_sparse: dim %d unsupported (<= 512, %% 4 == 0)", dim);
+  if (dx_planes && ((dim & 15) || ((uintptr_t)dx_planes & 15))) return fail(MT_ERR_ARG, "mt_layernorm_bwd_rows_sums_sparse: plane output needs dim %% 16 == 0 and 16-byte alignment");
+  if (rows <= 0 || period <= 0 || rows % period) return fail(MT_ERR_ARG, "mt_layernorm_bwd_rows_sums_sparse: rows %d must be a positive multiple of period %d", rows, period);
+  const int rp = (rows + 31) & ~31;
+  const PlaneRef dxp{reinterpret_cast<__bf16*>(dx_planes), (int64_t)rp * dim, dim >> 4, rp};
+  hipLaunchKernelGGL(layernorm_bwd_rows_sums_sparse_kernel, dim3(ln_rows_blocks(rows)), dim3(256), 0, (hipStream_t)stream, dy, x, stats,
+                     gamma, dx, dx_res, period, rows, dim, dxp, partials, skip_period);
+  return check_launch("mt_layernorm_bwd_rows_sums_sparse");
+}
+
 extern "C" int mt_layernorm_bwd_cols_reduce(const float* partials, int blocks, int dim, float* dgamma, float* dbeta, float* dx_colsum,
                                             void* stream) {
   if (!partials || !dgamma || !dbeta) return fail(MT_ERR_ARG, "mt_layernorm_bwd_cols_reduce: null pointer");
@@ -1802,7 +1849,7 @@ extern "C" int mt_attn_bwd(const float* qkv, const float* dout, float* dqkv, con
   // (few patches, many heads) takes the full-row form, or the scalars would land in the next clip and past the buffer.
   const bool fact_fits = (int64_t)2 * H * ((N + H * DH - 1) / (H * DH)) <= N - 1;
   const bool fact = fact_fits && dqkv_planes && (mode == 1 || (mode == 0 && (F == 8 || F == 16)));
-  hipLaunchKernelGGL(attn_cls_bwd_kernel, dim3(B * H), dim3(CLS_W * 64), (2 * N + CLS_W + 4 + CLS_W * 64) * sizeof(float), s, qkv, dout, dqkv, mask, B, H, F, n, scale, fact ? 1 : 0);
+  hipLaunchKernelGGL(attn_cls_bwd_kernel<false>, dim3(B * H), dim3(CLS_W * 64), (2 * N + CLS_W + 4 + CLS_W * 64) * sizeof(float), s, qkv, dout, dqkv, mask, B, H, F, n, scale, fact ? 1 : 0, PlaneRef{});
   int rc = check_launch("mt_attn_bwd(cls)");
   if (rc || mode == 2) return rc;                 // mode 2: the cls query's adjoint only (dk / dv of every key, dq of the cls row)
   // deterministic mode: the cls key's dk / dv (one row per (b, head), shared by every frame / patch group) go through a log with one
@@ -1841,4 +1888,19 @@ extern "C" int mt_attn_bwd(const float* qkv, const float* dout, float* dqkv, con
   // the cls query's contribution only -- the planes are the result
   hipLaunchKernelGGL(attn_bwd_cls_planes_kernel, dim3(B + (rp > B * N ? 1 : 0)), dim3(256), 0, s, dqkv, B, N, ld, dp);
   return check_launch("mt_attn_bwd(cls planes)");
+}
+
+extern "C" int mt_attn_bwd_cls_planes(const float* qkv, const float* dout, const uint8_t* mask, int B, int H, int F, int n, float scale,
+                                      void* dqkv_planes, void* stream) {
+  if (!qkv || !dout || !dqkv_planes) return fail(MT_ERR_ARG, "mt_attn_bwd_cls_planes: null pointer");
+  if (B < 1 || H < 1 || F < 1) return fail(MT_ERR_ARG, "mt_attn_bwd_cls_planes: bad shape");
+  if (n < 1 || n > 100) return fail(MT_ERR_UNSUPPORTED, "mt_attn_bwd_cls_planes: num-patches %d unsupported (1..100)", n);
+  if ((uintptr_t)dqkv_planes & 15) return fail(MT_ERR_ARG, "mt_attn_bwd_cls_planes: plane output needs 16-byte alignment");
+  const int N = 1 + F * n;
+  const int rp = (B * N + 31) & ~31, ld = 3 * H * DH;
+  const PlaneRef dp{reinterpret_cast<__bf16*>(dqkv_planes), (int64_t)rp * ld, ld / 16, rp};
+  // one block per (clip, head) and no atomics: nothing for the deterministic mode to replace
+  hipLaunchKernelGGL(attn_cls_bwd_kernel<true>, dim3(B * H + (rp > B * N ? 1 : 0)), dim3(CLS_W * 64),
+                     (2 * N + CLS_W + 4 + CLS_W * 64) * sizeof(float), (hipStream_t)stream, qkv, dout, nullptr, mask, B, H, F, n, scale, 0, dp);
+  return check_launch("mt_attn_bwd_cls_planes");
 }

@@ -103,11 +103,13 @@ LAUNCHES = {
     "mt_layernorm_bwd_rows": [f32p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "mt_layernorm_bwd_cols": [f32p] * 7 + [C.c_int, C.c_int, C.c_int, C.c_void_p],
     "mt_layernorm_bwd_rows_sums": [f32p] * 6 + [C.c_int, C.c_int, C.c_void_p, f32p, C.c_int, C.c_void_p],
+    "mt_layernorm_bwd_rows_sums_sparse": [f32p] * 6 + [C.c_int, C.c_int, C.c_int, C.c_void_p, f32p, C.c_int, C.c_void_p],
     "mt_layernorm_bwd_cols_reduce": [f32p, C.c_int, C.c_int, f32p, f32p, f32p, C.c_void_p],
     "mt_colsum": [f32p, i64, RowMap, C.c_int, C.c_int, f32p, C.c_void_p],
     "mt_head_bwd": [f32p] * 10 + [C.c_int] * 4 + [C.c_float, C.c_void_p],
     "mt_embed_bwd": [f32p] * 4 + [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p],
     "mt_attn_bwd": [f32p, f32p, f32p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p, C.c_void_p],
+    "mt_attn_bwd_cls_planes": [f32p, f32p, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p],
     "mt_bn_act_bwd": [f32p] * 9 + [C.c_void_p, C.c_int, i64, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "mt_bn_bwd_finalize": [C.c_void_p, C.c_int, C.c_double] + [f32p] * 5 + [C.c_int, C.c_int, C.c_void_p],
     "mt_se_bwd": [f32p] * 17 + [C.c_int] * 5 + [f32p, C.c_void_p],

@@ -147,7 +147,8 @@ def tsf_forward(model, feat, aux, params, B, F, n, save):
         if side.enabled:       # with MT_SIDE_STREAM=0 the transposes would sit on the critical path: the NN form is used instead
             cache["serial"] = cache.get("serial", 0) + 1       # a later forward rewrites the buffers: backward checks this
             saved["wT"], saved["wT_ready"], saved["wT_serial"] = cache["holder"], side.launch(transpose_all, reads=wts), cache["serial"]
-    # Optional (MT_TSF_PRUNE_LAST=1, off by default): dead-row pruning of the LAST layer.  The classification head reads the cls
+    # Optional on this engine (MT_TSF_PRUNE_LAST=1, off by default here; the plane path, tsf_planes.prune_last, has it on by default from 32 clips up):
+    # dead-row pruning of the LAST layer.  The classification head reads the cls
     # token only (size_invariant_timesformer.py:270-276), so everything the last layer computes for the 392 patch rows AFTER its
     # time attention is never read: the space attention's patch queries and out-projection rows and the whole feed-forward block
     # (the reference computes them and throws them away; their gradients are exactly zero).  With the switch on those rows are not
@@ -248,7 +249,7 @@ class _TSFFunction(torch.autograd.Function):
             stream = torch.cuda.current_stream(feat.device).cuda_stream
             key = ("tsf", B, F, n, feat.dtype, model.training, model.require_attention, L.deterministic(),
                    tuple(ctx.needs_input_grad[3:]), stream, os.environ.get("MT_PLANES_STREAMK", "0"),
-                   tuple(getattr(aux, nm) is None for nm in _AUX))
+                   tuple(getattr(aux, nm) is None for nm in _AUX), tsf_planes.prune_last(model, B))
 
         def body(ins, plan):
             a = aux if plan is None else types.SimpleNamespace(err=aux.err, **{nm: ins["aux_" + nm] for nm in _AUX})
@@ -256,7 +257,7 @@ class _TSFFunction(torch.autograd.Function):
                 logits, s_att, t_att, saved = tsf_planes.tsf_forward_planes(model, ins["feat"], a, params, B, F, n, save)
             elif tsf_planes.dropout_active(model):
                 raise NotImplementedError("attn-dropout / ff-dropout > 0 in train mode runs on the plane path only (MT_TSF_PLANES=1, "
-                                          "MT_GEMM_SPLIT=1, no MT_TSF_PRUNE_LAST, not under stream capture)")
+                                          "MT_GEMM_SPLIT=1, not under stream capture)")
             else:
                 logits, s_att, t_att, saved = tsf_forward(model, ins["feat"], a, params, B, F, n, save)
             if saved is not None:

@@ -14,6 +14,13 @@ LDS-DMA -- no operand is split inside a GEMM, none is split twice, and the weigh
 
 fp32 tensors that no longer exist: xn, h, du.  Selected by tsf_engine when the split-operand pipe is on (MT_TSF_PLANES=0 keeps the
 in-kernel split).
+
+From 32 clips up the LAST layer runs with its dead rows pruned (prune_last): the head reads x[:, 0] only
+(size_invariant_timesformer.py:270-276), so what that layer computes for the patch rows after its time attention is never read and its gradient is exactly zero.  The space
+attention keeps its LayerNorm and QKV GEMM on planes for all rows (the cls query attends to every key); the cls query's attention, the
+out-projection, LayerNorm -> FF1 + GEGLU -> FF2 and the head run on the B cls rows through mt_gemm with row strides.  Backward: the
+same tail on B rows, mt_attn_bwd_cls_planes for the complete dqkv planes, and mt_layernorm_bwd_rows_sums_sparse to bring the cls
+rows' residual gradient back into the full-row stream that the time attention's backward reads.
 """
 import os
 
@@ -30,8 +37,6 @@ _SEL = (2, 3, 7, 8, 12, 14)      # offsets of w_qkv, w_o (time); w_qkv, w_o (spa
 def eligible(model, M, save):
     if os.environ.get("MT_TSF_PLANES", "1") == "0" or not L.gemm_split_enabled():
         return False
-    if os.environ.get("MT_TSF_PRUNE_LAST", "0") != "0":
-        return False
     if torch.cuda.is_current_stream_capturing() and save:
         return False
     D, inner = model.dim, model.heads * model.dim_head
@@ -41,6 +46,21 @@ def eligible(model, M, save):
 def dropout_active(model):
     """nn.Dropout is the identity in eval mode (size_invariant_timesformer.py:66-70, 98-101)."""
     return model.training and (float(model.attn_dropout) > 0.0 or float(model.ff_dropout) > 0.0)
+
+
+PRUNE_MIN_CLIPS = 32     # smallest batch at which the pruned step was measured faster (profiles/prune_last_planes_ab.txt)
+
+
+def prune_last(model, B):
+    """Last layer on the cls rows only.  MT_TSF_PRUNE_LAST unset: from PRUNE_MIN_CLIPS clips up -- the rows removed scale with B, the
+    B-row mt_gemm launches that replace them (one 32-row tile strip each, K walked serially) cost about the same at any B <= 32, so
+    below ~20 clips the main queue gets longer, and nothing between 20 and 32 was measured.  =1: at any B; =0: never.
+    Full rows in every case while a dropout is active (the reference draws its multipliers in the shape [M, .] of all rows) and for
+    dim > 512 (mt_layernorm_bwd_rows_sums_sparse, like the dense rows + sums form, holds a row in registers up to 512 columns)."""
+    flag = os.environ.get("MT_TSF_PRUNE_LAST")
+    if flag == "0" or dropout_active(model) or model.dim > 512:
+        return False
+    return flag is not None or B >= PRUNE_MIN_CLIPS
 
 
 def _dropout_mult(model, shape, p, dev):
@@ -102,6 +122,7 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
     saved = {"layers": [], "planes": True, "wp": wp, "w_serial": serial} if save else None
     drop = dropout_active(model)
     p_att, p_ff = (float(model.attn_dropout), float(model.ff_dropout)) if drop else (0.0, 0.0)
+    prune = prune_last(model, B)
     want_att = model.require_attention
     s_att = t_att = None
     xn_p = L.planes_empty(M, D, dev)
@@ -127,6 +148,17 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
                     t_att = att
                 else:
                     s_att = att
+            if last and mode == 1 and prune:
+                # cls query only (row 0 of each clip of o; the other rows are neither written nor read); out-projection + residual on
+                # the B cls rows: row stride N, no gather
+                o = _new(dev, M, inner)
+                L.mt.attn_fwd(qkv, o, att, aux.mask, aux.ident, B, H, F, n, 2, scale, None)
+                x_cls = _new(dev, B, D)
+                L.gemm(L.OP_NT, o, w_o, x_cls, B, D, inner, N * inner, inner, D, epilogue=L.EPI_BIAS_RES, bias=b_o, R=x, ldr=N * D)
+                if save:
+                    rec[mode] = dict(x=x, stats=stats, xn_p=xn_p, qkv=qkv, o=o, dm=None)
+                x = x_cls
+                continue
             L.mt.attn_fwd(qkv, None, att, aux.mask, aux.ident, B, H, F, n, mode, scale, o_p)      # o leaves the kernels as planes only
             x_new = _new(dev, B, N, D) if save else x
             dm = None
@@ -143,6 +175,20 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
                 rec[mode] = dict(x=x, stats=stats, xn_p=xn_p, qkv=qkv, o_p=o_p, dm=dm)
             x = x_new
         g, b_, w1, b1, w2, b2 = next(it), next(it), next(it), next(it), next(it), next(it)
+        if last and prune:
+            # feed-forward block on the cls rows (x is [B, D] here)
+            xn_c, h_c, stats_c = _new(dev, B, D), _new(dev, B, 4 * D), (_new(dev, B, 2) if save else None)
+            u_c = _new(dev, B, 8 * D) if save else None
+            L.mt.layernorm_fwd(x, g, b_, xn_c, stats_c, B, D, eps, None)
+            L.gemm(L.OP_NT, xn_c, w1, h_c, B, 8 * D, D, D, D, 4 * D, epilogue=L.EPI_GEGLU, bias=b1, C2=u_c, ldc2=8 * D, n_half=4 * D)
+            x_out = _new(dev, B, 1, D)
+            L.gemm(L.OP_NT, h_c, w2, x_out, B, D, 4 * D, 4 * D, 4 * D, D, epilogue=L.EPI_BIAS_RES, bias=b2, R=x, ldr=D)
+            if save:
+                rec[2] = dict(x=x, xn=xn_c, stats=stats_c, u=u_c, h=h_c, dm=None)
+                saved["layers"].append(rec)
+                saved["pruned_last"] = True
+            x = x_out
+            continue
         if save:
             xn_p, h_p, stats = L.planes_empty(M, D, dev), L.planes_empty(M, 4 * D, dev), _new(dev, M, 2)
             u = _new(dev, M, 8 * D)
@@ -169,7 +215,7 @@ def tsf_forward_planes(model, feat, aux, params, B, F, n, save):
         x = x_new
     g, b_, w_h, b_h = next(it), next(it), next(it), next(it)
     logits = _new(dev, B, model.num_classes)
-    L.mt.head_fwd(x, g, b_, w_h, b_h, logits, B, x.shape[1], D, model.num_classes, eps)
+    L.mt.head_fwd(x, g, b_, w_h, b_h, logits, B, x.shape[1], D, model.num_classes, eps)      # x: [B, N, D], or [B, 1, D] after pruning
     if save:
         saved["x_final"] = x
     return logits, s_att, t_att, saved
@@ -231,16 +277,68 @@ def tsf_backward_planes(model, feat, aux, params, dims, saved, dlogits, need_dfe
     # ---- head
     i0 = take(4)
     g, b_, w_h, b_h = P[i0:i0 + 4]
-    dx = L.zeros((B, N, D), torch.float32, dev)
-    L.mt.head_bwd(dlogits, saved["x_final"], g, b_, w_h, dx, grads[i0], grads[i0 + 1], grads[i0 + 2], grads[i0 + 3], B, N, D,
+    pruned = bool(saved.get("pruned_last"))           # the last layer ran its tail on the cls rows only: the head saw [B, 1, D]
+    Nh = 1 if pruned else N
+    dx = L.zeros((B, Nh, D), torch.float32, dev)
+    L.mt.head_bwd(dlogits, saved["x_final"], g, b_, w_h, dx, grads[i0], grads[i0 + 1], grads[i0 + 2], grads[i0 + 3], B, Nh, D,
                   model.num_classes, eps)
-    dx2 = dx.view(M, D)
-    dx_p = L.split_planes_blk(dx2, M, D)
+    dx2 = dx.view(B * Nh, D)
+    dx_p = None if pruned else L.split_planes_blk(dx2, M, D)
     do = torch.empty(M, inner, dtype=torch.float32, device=dev)
     dqkv = torch.empty(M, 3 * inner, dtype=torch.float32, device=dev)     # scratch of mt_attn_bwd (main stream only)
 
-    for li in reversed(range(model.depth)):
-        rec = saved["layers"][li]
+    def cls_wgrad(A, Bm, out, M_, N_, lda, ldb, bias_out=None):
+        """dW[M_, N_] += A^T Bm over the B cls rows (fp32 operands, row strides lda / ldb), + the bias gradient = column sums of A."""
+        def run():
+            L.gemm(L.OP_TN, A, Bm, out, M_, N_, B, lda, ldb, N_, epilogue=L.EPI_ATOMIC, split_k=0)
+            if bias_out is not None:
+                L.mt.colsum(A, lda, L.RowMap(0, 0, 0), B, M_, bias_out)
+        return side.launch(run, reads=(A, Bm))
+
+    def pruned_tail(li, rec, dx_c):
+        """The last layer below the head down to its space attention's LayerNorm, on the cls rows: dx_c [B, D] is the gradient of the
+        layer's output.  Returns the full-row (dx2, dx_p) that the time attention's backward reads."""
+        # ---- feed-forward (fp32 operands through mt_gemm)
+        i0 = take(6)
+        g, b_, w1, b1, w2, b2 = P[i0:i0 + 6]
+        r = rec[2]
+        du_c = torch.empty(B, 8 * D, dtype=torch.float32, device=dev)
+        dxn_c = torch.empty(B, D, dtype=torch.float32, device=dev)
+        cls_wgrad(dx_c, r["h"], grads[i0 + 4], D, 4 * D, D, 4 * D, bias_out=grads[i0 + 5])
+        L.gemm(L.OP_NN, dx_c, w2, du_c, B, 4 * D, D, D, 4 * D, 8 * D, epilogue=L.EPI_GEGLU_BWD, C2=r["u"], ldc2=8 * D, n_half=4 * D,
+               col_sum=grads[i0 + 3])
+        cls_wgrad(du_c, r["xn"], grads[i0 + 2], 8 * D, D, 8 * D, D)
+        L.gemm(L.OP_NN, du_c, w1, dxn_c, B, D, 8 * D, 8 * D, D, D)
+        # B rows: the fused LayerNorm backward (gamma / beta gradients and the column sums for the space to_out.0.bias in the same launch),
+        # out of place -- the weight gradient above may still be reading dx_c
+        dx_s = torch.empty(B, D, dtype=torch.float32, device=dev)
+        L.mt.layernorm_bwd(dxn_c, r["x"], r["stats"], g, dx_s, grads[i0], grads[i0 + 1], B, D, 1, grads[i0 - 1], 0, dx_c)
+        if not keep_saved:
+            r.clear()
+        # ---- space attention: out-projection on the cls rows of o (row stride N * inner), the cls query's adjoint as complete dqkv
+        # planes, then the QKV layer's two gradients over all rows
+        i0 = take(5)
+        g, b_, w_qkv, w_o, b_o = P[i0:i0 + 5]
+        r = rec[1]
+        cls_wgrad(dx_s, r["o"], grads[i0 + 3], D, inner, D, N * inner)
+        L.gemm(L.OP_NN, dx_s, w_o, do, B, inner, D, D, inner, N * inner)         # row 0 of each clip's do; the rest is not read
+        dqkv_p = L.planes_empty(M, 3 * inner, dev)
+        L.mt.attn_bwd_cls_planes(r["qkv"], do, aux.mask, B, H, F, n, scale, dqkv_p)
+        wgrad(dqkv_p, r["xn_p"], grads[i0 + 2], 3 * inner, D)
+        dxn = torch.empty(M, D, dtype=torch.float32, device=dev)
+        L.gemm_planes(L.OP_NN, dqkv_p, wp[(li, 7)], M, D, 3 * inner, Cout=dxn, ldc=D)
+        # dx = LN'(dxn) on every row + the residual gradient on the cls rows; its column sums -> time to_out.0.bias
+        dx_new = torch.empty(M, D, dtype=torch.float32, device=dev)
+        dx_new_p = L.planes_empty(M, D, dev)
+        nb = lib.mt_layernorm_bwd_rows_blocks(M)
+        part = _new(dev, nb, 3, D)
+        L.mt.layernorm_bwd_rows_sums_sparse(dxn, r["x"], r["stats"], g, dx_new, dx_s, N, M, D, dx_new_p, part, 0)
+        side.launch(lambda: L.mt.layernorm_bwd_cols_reduce(part, nb, D, grads[i0], grads[i0 + 1], grads[i0 - 1]), reads=(part,))
+        if not keep_saved:
+            r.clear()
+        return dx_new, dx_new_p
+
+    def ff_block(li, rec, dx2, dx_p):
         # ---- feed-forward: x_out = h W2^T + b2 + x ; h = a*gelu(g) ; [a|g] = LN(x) W1^T + b1
         i0 = take(6)
         g, b_, w1, b1, w2, b2 = P[i0:i0 + 6]
@@ -266,8 +364,18 @@ def tsf_backward_planes(model, feat, aux, params, dims, saved, dlogits, need_dfe
         dx2, dx_p = ln_bwd(dxn, r, g, dx2, i0, None if rec[1].get("dm") is not None else grads[i0 - 1], 0)
         if not keep_saved:
             r.clear()
+        return dx2, dx_p
+
+    for li in reversed(range(model.depth)):
+        rec = saved["layers"][li]
+        if pruned and li == model.depth - 1:
+            dx2, dx_p = pruned_tail(li, rec, dx2)
+            modes = (0,)
+        else:
+            dx2, dx_p = ff_block(li, rec, dx2, dx_p)
+            modes = (1, 0)
         # ---- attention blocks: x_out = o Wo^T + bo + x ; o = attn(qkv) ; qkv = LN(x) Wqkv^T
-        for mode in (1, 0):
+        for mode in modes:
             i0 = take(5)
             g, b_, w_qkv, w_o, b_o = P[i0:i0 + 5]
             r = rec[mode]
